@@ -8,18 +8,24 @@ GLOBAL batch 65 536 (BASELINE configs[2]).  `--gpus N` shards that batch over N 
 65 536 instances on one GPU, N = 8 runs 8 192 per GPU); with more than one rank a step ends with the single RCCL
 all-gather of the 80-byte output records, issued on a side stream so that it overlaps the next step's kernel.
 
-`other_configs` (always emitted at N = 1): BASELINE configs[1] (1 024 instances, Formulation B), configs[3] (walking gait,
-Formulation A, C = 150, 16 384 instances) and the per-GPU shape of configs[4] (Monte-Carlo trot/walk, C = 200, 16 384
-instances per GPU), each with its own roofline and cpu_baseline.  At N > 1 configs[4] runs 16 384 instances on every
-rank (131 072 at N = 8) with the same all-gather.
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, runs W warm-up steps, times ONE region of exactly K steps
+(bracketed by barrier + synchronize on both sides, wall time = max over ranks), writes the last step's output records if
+--dump-outputs DIR is given (DIR/<field>.npy, float64) and prints the headline line: metric, value, unit, ms_per_step,
+higher_is_better, dtype, config.
 
-    python bench.py                       # 1 GPU
+--full adds everything else.  The headline's regions of exactly K steps repeat until at least --min-region-ms of timed work
+exists (K = 20 steps of a 56 us kernel is 1 ms) and the MEDIAN region is reported; then its roofline (the dominant kernel
+alone), the host-path extras and `other_configs` (at N = 1): BASELINE configs[1] (1 024 instances, Formulation B), configs[3]
+(walking gait, Formulation A, C = 150, 16 384 instances) and the per-GPU shape of configs[4] (Monte-Carlo trot/walk, C = 200,
+16 384 instances per GPU), each with its own roofline and cpu_baseline.  At N > 1 configs[4] runs 16 384 instances on every
+rank (131 072 at N = 8) with the same all-gather.  --only <leg> runs one leg with all of its own measurements.
+
+    python bench.py                       # 1 GPU, headline only
+    python bench.py --full                # 1 GPU, every leg
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
-Timing: W warm-up steps, then regions of EXACTLY K steps each, bracketed by barrier + synchronize on both sides, wall time
-= max over ranks; regions repeat until at least --min-region-ms of timed work exists (K = 20 steps of a 56 us kernel is
-1 ms) and the MEDIAN region is reported.  Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.
 
 cpu_baseline: the CPU oracle with the reference's own vendored qpOASES (oracle/_ref) on the box's host cores, in worker
 processes that never touch the GPU (`bench.py --cpu-worker ...`).
@@ -328,9 +334,10 @@ class Ranks:
             self.dist.destroy_process_group()
 
 
-def timed_regions(R, step, K, W, min_ms, drain=None, ev=None, prep=None):
+def timed_regions(R, step, K, W, min_ms, drain=None, ev=None, prep=None, min_regions=3):
     """W warm-up steps; then regions of exactly K steps, barrier + synchronize on both sides, max over ranks; regions repeat
-    until min_ms of timed work (at least 3).  ev = (record_start, record_end) hooks on the launch stream, per region.
+    until min_ms of timed work (at least min_regions; min_regions=1 with min_ms=0: ONE region, exactly K timed steps).
+    ev = (record_start, record_end) hooks on the launch stream, per region.
     prep() runs BEFORE a region's opening barrier (untimed): it puts the region's inputs in place (HBM-resident when the clock starts)."""
     torch = R.torch
     if prep:
@@ -356,7 +363,7 @@ def timed_regions(R, step, K, W, min_ms, drain=None, ev=None, prep=None):
         torch.cuda.synchronize(); R.barrier()
         el = R.max(time.perf_counter() - t0)
         walls.append(el); total += el; n += 1
-        if (n >= 3 and total >= min_ms * 1e-3) or n >= 400:
+        if (n >= min_regions and total >= min_ms * 1e-3) or n >= 400:
             break
     return walls
 
@@ -562,9 +569,11 @@ def kernel_name_b(N, B, cus, sweep=False, deferring=False):
     return "ismpc_tick_quad<%d, %d, false>" % (_quad_r(N, lpi), lpi)
 
 
-def leg_b(R, q, leg, N, global_batch, K, W, min_ms, extras, sweep_sets=0):
+def leg_b(R, q, leg, N, global_batch, K, W, min_ms, extras, sweep_sets=0, detail=True):
     """Formulation B: `global_batch` instances sharded over the ranks; returns the result dict (rank 0) or None.
-    sweep_sets > 0: a parameter sweep (ismpc_create_sweep) -- instance i runs with parameter set i % sweep_sets."""
+    sweep_sets > 0: a parameter sweep (ismpc_create_sweep) -- instance i runs with parameter set i % sweep_sets.
+    detail=False (a plain run): ONE region of exactly K timed steps and nothing after it (no roofline, no collective timing).
+    The result's "_outputs" holds the records of the last timed step (the gathered global batch when there is a collective)."""
     torch = R.torch
     from quadruped_gait_generation_ismpc_amd import workload
     from quadruped_gait_generation_ismpc_amd.distributed import shard_range, GatherPipeline
@@ -615,48 +624,62 @@ def leg_b(R, q, leg, N, global_batch, K, W, min_ms, extras, sweep_sets=0):
             pipe.after_launch(k, d_out[b])                               # the one collective of the path, on the side stream
 
     ev = RegionEvents(torch)
-    walls = timed_regions(R, step, K, W, min_ms, drain=(grp.sync if grp else (pipe.drain if pipe else None)), ev=(ev.start, ev.end))
+    walls = timed_regions(R, step, K, W, min_ms if detail else 0.0, drain=(grp.sync if grp else (pipe.drain if pipe else None)), ev=(ev.start, ev.end),
+                          min_regions=3 if detail else 1)
     wall = statistics.median(walls)
     step_interval_ms = ev.median_ms(K) if grp is None else 1e3 * wall / K      # (the group launches on its own streams: events on torch's stream do not see them)
-    if grp is not None:
-        solver.solve_batch_torch(d_in, d_out[0])                         # this rank's shard through the plain handle: what the gathered buffer must hold at [first, first + B)
+    allout = None
+    if not detail:
+        # a plain run stops here: the records of the last timed step, nothing launched after it
+        if grp is not None:
+            allout = q.from_device(grp.result_torch(global_batch, 0, (K - 1) & 1).clone(), q.TICK_OUT)
+            out = allout[first:first + B]
+        elif pipe is not None:
+            allout = pipe.result_numpy((K - 1) & 1, q.TICK_OUT)
+            out = allout[rank * B:(rank + 1) * B]
+        else:
+            out = q.from_device(d_out[0], q.TICK_OUT)
+        kernel_ms_train = collective_ms = None                             # (measured by --full only)
+    else:
+        if grp is not None:
+            solver.solve_batch_torch(d_in, d_out[0])                         # this rank's shard through the plain handle: what the gathered buffer must hold at [first, first + B)
 
-    # ---- dominant kernel alone (roofline): same inputs.  Two durations: a train of K back-to-back launches (per-launch
-    # interval, event pair per region) and ONE launch between synchronisations (what rocprofv3 reports per dispatch)
-    solo = solver
-    deferring = bool(((q.from_device(d_out[0], q.TICK_OUT)["status"] & q.ST_Z_INEQ_ACTIVE) != 0).any())
-    two_launches = not one_launch(N, B, cus) or (deferring and not _resident(B, cus) and os.environ.get("ISMPC_ONE_LAUNCH") != "3")
-    if two_launches:
-        os.environ["ISMPC_Z_FALLBACK"] = "0"                             # the tick kernel alone: the second launch (fallback) switched off
-        try:
-            solo = (q.MPCSolver.sweep(q.reference_plan(params=p), workload.make_sweep_params(sweep_sets, N=N), device=R.local_rank) if sweep_sets > 0
-                    else q.MPCSolver(q.reference_plan(params=p), params=p, device=R.local_rank))
-        finally:
-            del os.environ["ISMPC_Z_FALLBACK"]
-        if sweep_sorted:
-            solo.sweep_bind(d_in)
-    d_tmp = torch.empty_like(d_out[0])
-    ev2 = RegionEvents(torch)
-    timed_regions(R, lambda k: solo.solve_batch_torch(d_in, d_tmp), K, W, min_ms, ev=(ev2.start, ev2.end))
-    kernel_ms_train = ev2.median_ms(K)
-    kernel_ms = isolated_ms(torch, lambda: solo.solve_batch_torch(d_in, d_tmp))
-    collective_ms = None
-    if grp is not None:
-        # the collective alone: steps whose kernels are already done do not exist in this API, so time a train of full steps against the
-        # kernel train measured above -- the difference is what the all-gather adds when it does NOT hide behind the next kernel
-        collective_ms = max(0.0, 1e3 * wall / K - kernel_ms_train)
-    if pipe is not None:
-        ev3 = RegionEvents(torch)
-        timed_regions(R, lambda k: pipe.gather_blocking(d_out[0]), K, W, min_ms, ev=(ev3.start, ev3.end))
-        collective_ms = ev3.median_ms(K) if not R.rehearse else None
+        # ---- dominant kernel alone (roofline): same inputs.  Two durations: a train of K back-to-back launches (per-launch
+        # interval, event pair per region) and ONE launch between synchronisations (what rocprofv3 reports per dispatch)
+        solo = solver
+        deferring = bool(((q.from_device(d_out[0], q.TICK_OUT)["status"] & q.ST_Z_INEQ_ACTIVE) != 0).any())
+        two_launches = not one_launch(N, B, cus) or (deferring and not _resident(B, cus) and os.environ.get("ISMPC_ONE_LAUNCH") != "3")
+        if two_launches:
+            os.environ["ISMPC_Z_FALLBACK"] = "0"                             # the tick kernel alone: the second launch (fallback) switched off
+            try:
+                solo = (q.MPCSolver.sweep(q.reference_plan(params=p), workload.make_sweep_params(sweep_sets, N=N), device=R.local_rank) if sweep_sets > 0
+                        else q.MPCSolver(q.reference_plan(params=p), params=p, device=R.local_rank))
+            finally:
+                del os.environ["ISMPC_Z_FALLBACK"]
+            if sweep_sorted:
+                solo.sweep_bind(d_in)
+        d_tmp = torch.empty_like(d_out[0])
+        ev2 = RegionEvents(torch)
+        timed_regions(R, lambda k: solo.solve_batch_torch(d_in, d_tmp), K, W, min_ms, ev=(ev2.start, ev2.end))
+        kernel_ms_train = ev2.median_ms(K)
+        kernel_ms = isolated_ms(torch, lambda: solo.solve_batch_torch(d_in, d_tmp))
+        collective_ms = None
+        if grp is not None:
+            # the collective alone: steps whose kernels are already done do not exist in this API, so time a train of full steps against the
+            # kernel train measured above -- the difference is what the all-gather adds when it does NOT hide behind the next kernel
+            collective_ms = max(0.0, 1e3 * wall / K - kernel_ms_train)
+        if pipe is not None:
+            ev3 = RegionEvents(torch)
+            timed_regions(R, lambda k: pipe.gather_blocking(d_out[0]), K, W, min_ms, ev=(ev3.start, ev3.end))
+            collective_ms = ev3.median_ms(K) if not R.rehearse else None
 
-    out = q.from_device(d_out[0], q.TICK_OUT)
-    if grp is not None:
-        allout = q.from_device(grp.result_torch(global_batch, 0, (K - 1) & 1).clone(), q.TICK_OUT)
-        assert allout[first:first + B].tobytes() == out.tobytes(), "group all-gather misplaced or altered this rank's shard"
-    if pipe is not None:
-        allout = pipe.result_numpy((K - 1) & 1, q.TICK_OUT)
-        assert allout[rank * B:(rank + 1) * B].tobytes() == q.from_device(d_out[(K - 1) & 1], q.TICK_OUT).tobytes(), "all-gather misplaced this rank's shard"
+        out = q.from_device(d_out[0], q.TICK_OUT)
+        if grp is not None:
+            allout = q.from_device(grp.result_torch(global_batch, 0, (K - 1) & 1).clone(), q.TICK_OUT)
+            assert allout[first:first + B].tobytes() == out.tobytes(), "group all-gather misplaced or altered this rank's shard"
+        if pipe is not None:
+            allout = pipe.result_numpy((K - 1) & 1, q.TICK_OUT)
+            assert allout[rank * B:(rank + 1) * B].tobytes() == q.from_device(d_out[(K - 1) & 1], q.TICK_OUT).tobytes(), "all-gather misplaced this rank's shard"
     st = out["status"]
     stage3 = (st & (q.ST_FLIGHT | q.ST_BAD_INDEX | q.ST_TICK_SKIPPED)) == 0
     itx, ity = out["iters"] & 255, (out["iters"] >> 8) & 255
@@ -666,8 +689,6 @@ def leg_b(R, q, leg, N, global_batch, K, W, min_ms, extras, sweep_sets=0):
     res = None
     if rank == 0:
         value = global_batch / (wall / K)
-        flops = flops_b(N) * B
-        kname = kernel_name_b(N, B, cus, sweep=sweep_sets > 0, deferring=deferring)
         res = {
             "value": value, "unit": "ticks/s (1 tick = one MPCSolver::solve = 3 QPs: vertical + x + y)",
             "ms_per_step": 1e3 * wall / K, "dtype": "f64", "qp_solves_per_s": 3.0 * value,
@@ -682,15 +703,19 @@ def leg_b(R, q, leg, N, global_batch, K, W, min_ms, extras, sweep_sets=0):
                        "infeasible_fraction": float(((st & (q.ST_X_INFEASIBLE | q.ST_Y_INFEASIBLE)) != 0).mean()),
                        "z_inequality_active_fraction": float(((st & q.ST_Z_INEQ_ACTIVE) != 0).mean()),
                        "active_box_fraction": active_box},
-            "roofline": roofline(leg, kname, kernel_ms, B, "f64", flops, 152.0 * B,
-                                 extra={"kernel_ms_train": kernel_ms_train, "step_interval_ms": step_interval_ms},
-                                 note="kernel_ms = ONE launch between synchronisations (HIP events; agrees with the rocprofv3 per-dispatch average under "
-                                      "profiles/r04); kernel_ms_train = per-launch interval of back-to-back launches of the same kernel (consecutive "
-                                      "launches overlap head to tail, so it is shorter and is what `value` is made of); step_interval_ms = the same for the "
-                                      "whole step (one launch while no instance has active vertical inequality rows; a batch beyond the resident size that "
-                                      "does defer instances takes two: the tick kernel, then one wavefront per deferred instance).  No MFMA on this "
-                                      "path: bound = FP64 vector issue."),
+            "_outputs": allout if allout is not None else out,
         }
+        if detail:
+            flops = flops_b(N) * B
+            kname = kernel_name_b(N, B, cus, sweep=sweep_sets > 0, deferring=deferring)
+            res["roofline"] = roofline(leg, kname, kernel_ms, B, "f64", flops, 152.0 * B,
+                                       extra={"kernel_ms_train": kernel_ms_train, "step_interval_ms": step_interval_ms},
+                                       note="kernel_ms = ONE launch between synchronisations (HIP events; agrees with the rocprofv3 per-dispatch average under "
+                                            "profiles/r04); kernel_ms_train = per-launch interval of back-to-back launches of the same kernel (consecutive "
+                                            "launches overlap head to tail, so it is shorter and is what `value` is made of); step_interval_ms = the same for the "
+                                            "whole step (one launch while no instance has active vertical inequality rows; a batch beyond the resident size that "
+                                            "does defer instances takes two: the tick kernel, then one wavefront per deferred instance).  No MFMA on this "
+                                            "path: bound = FP64 vector issue.")
         if grp is not None:
             from quadruped_gait_generation_ismpc_amd import group as G
             res["multi_gpu"] = {"rccl_world": grp.world, "rccl_version": G.rccl_version(), "path": "abi", "kernel_ms": kernel_ms_train,
@@ -1094,6 +1119,23 @@ def emit(full):
     print(compact_line(full, write_detail(full)), flush=True)
 
 
+DUMP_LIMIT = 64 << 20        # bytes of all --dump-outputs files together
+
+
+def dump_outputs(dirname, rec):
+    """--dump-outputs: the output records of the last timed step, one DIR/<field>.npy per field of the record, float64 (the integer
+    fields `status` and `iters` are exact in it).  A batch whose files would exceed DUMP_LIMIT is cut to a fixed, seeded sample of
+    records, in ascending order, whose indices go to DIR/index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    per_rec = sum(8 * int(np.prod(rec.dtype[n].shape or (1,))) for n in rec.dtype.names)
+    if len(rec) * per_rec > DUMP_LIMIT:
+        idx = np.sort(np.random.default_rng(0).choice(len(rec), size=(DUMP_LIMIT - 4096) // (per_rec + 8), replace=False))
+        rec = rec[idx]
+        np.save(os.path.join(dirname, "index.npy"), idx.astype(np.float64))
+    for n in rec.dtype.names:
+        np.save(os.path.join(dirname, n + ".npy"), np.ascontiguousarray(rec[n], dtype=np.float64))
+
+
 # ======================================================================================================================
 def main():
     if len(sys.argv) >= 3 and sys.argv[1] == "--cpu-worker":
@@ -1122,8 +1164,15 @@ def main():
                                                                                    "(include/ismpc_group.h; default) or torch.distributed's nccl backend (A/B)")
     ap.add_argument("--force-collective", action="store_true", help="build the RCCL group and run the path's all-gather even with ONE rank "
                                                                      "(exercises communicator set-up and the side-stream pipeline on a one-GPU box; moves no bytes between GPUs)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline's timed steps: its roofline timings, the host-path extras, the "
+                                                         "one-GPU RCCL group, the sustained closed loop, BASELINE's other configs and the cpu_baseline legs, "
+                                                         "with the headline timed in regions of --steps until --min-region-ms (a plain run: ONE region of exactly --steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the records the headline path returned in its last timed step "
+                                                                         "as DIR/<field>.npy (float64, one file per record field)")
     ap.add_argument("--launcher-selftest", type=int, default=None, help=argparse.SUPPRESS)   # rank that fails (-1: none); no GPU is touched
     args = ap.parse_args()
+    if args.dump_outputs and args.only and args.only in ("config3_walk_C150", "config4_mc_C200", "a_walk_C100", "a_trot_C160"):
+        raise SystemExit("--dump-outputs: Formulation B legs only (the headline, or --only with a Formulation B leg)")
     if os.environ.get("ISMPC_BENCH_CHILD") != "1" and (args.spawn or (args.gpus > 1 and "WORLD_SIZE" not in os.environ)):
         # the launcher never touches the GPU (a process that did must not be replaced or forked around): it only starts the ranks
         sys.exit(spawn_ranks(args.gpus, [a for a in sys.argv[1:] if a != "--spawn"]))
@@ -1146,7 +1195,8 @@ def main():
     a_steps = max(3, min(K, 10))                                        # Formulation A steps take milliseconds
 
     LEGS = {
-        "headline":         lambda: leg_b(R, q, "headline_b%d" % (args.global_batch // world), args.horizon, args.global_batch, K, W, M, extras=not args.no_extras),
+        "headline":         lambda detail=True: leg_b(R, q, "headline_b%d" % (args.global_batch // world), args.horizon, args.global_batch, K, W, M,
+                                                      extras=detail and not args.no_extras, detail=detail),
         "config1_b1024":    lambda: leg_b(R, q, "config1_b1024", args.horizon, 1024, K, W, M, extras=False),
         "shard_b8192":      lambda: leg_b(R, q, "shard_b8192", args.horizon, 8192, K, W, M, extras=False),
         "shard_b16384":     lambda: leg_b(R, q, "shard_b16384", args.horizon, 16384, K, W, M, extras=False),    # the per-GPU shards of the headline at N = 4, 2
@@ -1182,6 +1232,9 @@ def main():
             raise SystemExit(f"--only: unknown leg {args.only}")
         res = LEGS[args.only](args.dtype) if args.only in a_legs else LEGS[args.only]()
         if rank == 0:
+            outputs = res.pop("_outputs", None)
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, outputs)
             line = {"metric": "ISMPC QP solves/s (batch, N=100 horizon)" if args.only not in a_legs else "ISMPC ticks/s (Formulation A)"}
             line.update(res); line.update(common); line.setdefault("scaling", "strong")
             if args.only in a_legs:
@@ -1194,7 +1247,20 @@ def main():
         R.close()
         return
 
-    head = LEGS["headline"]()
+    head = LEGS["headline"](args.full)
+    if rank == 0:
+        outputs = head.pop("_outputs")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
+    if not args.full:
+        # a plain run: the headline's line and nothing else
+        if rank == 0:
+            line = {"metric": "ISMPC QP solves/s (batch, N=100 horizon)"}
+            line.update(head); line.update(common)
+            line["scaling"] = "strong"
+            emit(line)
+        R.close()
+        return
     others = []
     sustained = None
     if world == 1 and "multi_gpu" not in head:
@@ -1205,6 +1271,8 @@ def main():
         if world == 1:
             r1 = LEGS["config1_b1024"]()
             rs = LEGS["sweep_k64_b65536"]()
+            for r_ in (r1, rs):
+                r_.pop("_outputs")                                       # (--dump-outputs writes the headline's records only)
             r3 = LEGS["config3_walk_C150"]()
             r3f = LEGS["config3_walk_C150"]("f32") if have_f32 else None
         r4 = LEGS["config4_mc_C200"]()

@@ -64,7 +64,7 @@ h = line(os.path.join(P, "bench_full_line.json")) or line(os.path.join(P, "headl
 extra = []
 if h and "steps" in h and h.get("regions"):
     r = h["roofline"]
-    extra.append(f"The default `python bench.py` of the same session ({h['steps']} steps per region, {h['regions']} regions: the table's legs are the short profiled runs, "
+    extra.append(f"`python bench.py --full` of the same session ({h['steps']} steps per region, {h['regions']} regions: the table's legs are the short profiled runs, "
                  f"40 steps, 5 ms regions, and the chip clocks higher in the long one): **{h['value']:.3g} ticks/s**, {h['ms_per_step'] * 1e3:.1f} µs per step, "
                  f"`{r['kernel']}` {r['kernel_ms'] * 1e3:.1f} µs isolated / {r['kernel_ms_train'] * 1e3:.1f} µs in a train, `frac` {r.get('frac') or 0:.3f}.")
 if h:
@@ -92,7 +92,7 @@ if h:
         dl = line(os.path.join(P, "driver_cmd_bench_line.json"))
         top = [r for r in ks if h["roofline"]["kernel"] in r["Name"]]
         if top and dl:
-            extra.append(f"The exact driver command (`python3 bench.py --gpus 1 --steps 20 --warmup 5`) under rocprofv3 (`profiles/r04/driver_cmd_kernel_stats.csv`): "
+            extra.append(f"The full command (`python3 bench.py --full --gpus 1 --steps 20 --warmup 5`) under rocprofv3 (`profiles/r04/driver_cmd_kernel_stats.csv`): "
                          f"`{h['roofline']['kernel']}` {float(top[0]['AverageNs']) / 1e3:.1f} µs average over {top[0]['Calls']} launches of the whole process (isolated launches, "
                          f"the host-path calls and the group leg included; a launch alone is longer than its share of a train, see above), against `ms_per_step` "
                          f"{dl['ms_per_step'] * 1e3:.1f} µs, `roofline.kernel_ms_train` {dl['roofline']['kernel_ms_train'] * 1e3:.1f} µs and `kernel_ms` {dl['roofline']['kernel_ms'] * 1e3:.1f} µs of the "

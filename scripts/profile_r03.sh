@@ -65,6 +65,6 @@ fi
 # the complete line (every leg, host-path extras, cpu_baseline) and the box's VALU rates, when the whole set was regenerated
 if [ $ALL -eq 1 ]; then
   export ISMPC_PROFILES_DIR=$OUT
-  timeout -k 10 900 python3 $R/bench.py > $OUT/bench_full_line.json 2> $OUT/bench_full.err || { tail -5 $OUT/bench_full.err; exit 1; }
+  timeout -k 10 900 python3 $R/bench.py --full > $OUT/bench_full_line.json 2> $OUT/bench_full.err || { tail -5 $OUT/bench_full.err; exit 1; }
   [ -x $R/build/valu_peak ] && $R/build/valu_peak > $OUT/valu_peak.json
 fi

@@ -68,13 +68,13 @@ fi
 if [ $ALL -eq 1 ] || [ $ONLY_FINAL -eq 1 ]; then
   export ISMPC_PROFILES_DIR=$OUT
   [ -d $R/profiles/r04 ] && [ $ONLY_FINAL -eq 1 ] && export ISMPC_PROFILES_DIR=$R/profiles/r04      # the summaries of the earlier calls, already copied in place
-  # the EXACT driver command, once under rocprofv3 --kernel-trace --stats (its kernel_stats.csv: "dominant kernel time per step <= driver
-  # ms_per_step" can be checked from the files) and once plain (the line the driver would record + bench_detail.json)
+  # the full benchmark (--full: every leg), once under rocprofv3 --kernel-trace --stats (its kernel_stats.csv: "dominant kernel time per step <=
+  # ms_per_step" can be checked from the files) and once without the profiler (its line + bench_detail.json)
   rm -rf $OUT/tmp_driver; mkdir -p $OUT/tmp_driver
-  timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/tmp_driver/stats -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/driver_cmd_bench_line_profiled.json 2> $OUT/tmp_driver/stats.err || { tail -5 $OUT/tmp_driver/stats.err; exit 1; }
+  timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/tmp_driver/stats -- python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/driver_cmd_bench_line_profiled.json 2> $OUT/tmp_driver/stats.err || { tail -5 $OUT/tmp_driver/stats.err; exit 1; }
   cp $(find $OUT/tmp_driver/stats -name "*kernel_stats.csv" | head -1) $OUT/driver_cmd_kernel_stats.csv
   rm -rf $OUT/tmp_driver
-  timeout -k 10 900 python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/driver_cmd_bench_line.json 2> $OUT/bench_full.err || { tail -5 $OUT/bench_full.err; exit 1; }
+  timeout -k 10 900 python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/driver_cmd_bench_line.json 2> $OUT/bench_full.err || { tail -5 $OUT/bench_full.err; exit 1; }
   cp $R/bench_detail.json $OUT/bench_full_line.json
   [ -x $R/build/valu_peak ] && $R/build/valu_peak > $OUT/valu_peak.json
   [ -x $R/build/launch_floor ] && $R/build/launch_floor > $OUT/launch_floor.json      # what a launch costs before it does any work (scripts/micro/launch_floor.hip)

@@ -173,3 +173,25 @@ def test_source_hash_is_by_content_not_by_path(tmp_path, monkeypatch):
     assert B._stale(str(lib), [], "") is True                             # built from other sources than the tree holds now
     (tmp_path / "lib.so.src_sha256").write_text(B.source_sha256())
     assert B._stale(str(lib), [], "") is False and B._stale(str(lib), [], "-DX") is True
+
+
+def test_dump_outputs_writes_every_field_within_the_limit(bench, tmp_path, monkeypatch):
+    """--dump-outputs: one float64 .npy per record field (integers exact); a batch over the size limit is cut to a fixed, seeded
+    sample whose indices are written beside it."""
+    import numpy as np
+    b, _ = bench
+    rec = np.zeros(1000, dtype=[("com_pos", "<f8", 3), ("status", "<i4"), ("iters", "<i4")])
+    rec["com_pos"] = np.arange(3000).reshape(1000, 3) * 0.25
+    rec["status"] = np.arange(1000) * 7; rec["iters"] = (np.arange(1000) % 256) | (3 << 8)
+    b.dump_outputs(str(tmp_path / "all"), rec)
+    assert sorted(os.listdir(tmp_path / "all")) == ["com_pos.npy", "iters.npy", "status.npy"]
+    for n in rec.dtype.names:
+        a = np.load(tmp_path / "all" / (n + ".npy"))
+        assert a.dtype == np.float64 and (a == rec[n]).all()
+    monkeypatch.setattr(b, "DUMP_LIMIT", 4096 + 48 * 100)                # room for 100 records of 5 float64 values and their index
+    b.dump_outputs(str(tmp_path / "s1"), rec); b.dump_outputs(str(tmp_path / "s2"), rec)
+    idx = np.load(tmp_path / "s1" / "index.npy")
+    assert len(idx) == 100 and (np.diff(idx) > 0).all() and (idx == np.load(tmp_path / "s2" / "index.npy")).all()
+    k = idx.astype(np.int64)
+    assert (np.load(tmp_path / "s1" / "com_pos.npy") == rec["com_pos"][k]).all() and (np.load(tmp_path / "s1" / "status.npy") == rec["status"][k]).all()
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= b.DUMP_LIMIT + 4 * 128

@@ -28,7 +28,9 @@ def _check_roofline_full(rf, ms_per_step, need_counters):
         assert not need_counters, rf.get("note")
         assert rf["frac"] is None and rf["traffic"] is None and ("STALE" in rf["note"] or "no PMC summary" in rf["note"])
         return
-    assert rf["executed"] is not None and rf["pmc_lib_sha256"] == rf["lib_sha256"]
+    # the summary was collected from this library: the same binary, or the same sources built in another directory (the binary embeds its source paths)
+    assert rf["executed"] is not None and rf["pmc_matches_lib"] is True
+    assert rf["pmc_lib_sha256"] == rf["lib_sha256"] or (rf["src_sha256"] is not None and rf["pmc_src_sha256"] == rf["src_sha256"])
     assert abs(rf["frac"] - rf["achieved"] / rf["peak"]) <= 1e-9
     assert 0.0 < rf["frac"] <= 1.0
     assert 0.0 < rf["executed"]["valu_issue_frac"] <= 1.0                                  # executed work cannot exceed the pipe
@@ -48,7 +50,7 @@ def test_bench_line_contract(built_libs):
     detail_path = os.path.join(ROOT, "bench_detail.json")
     if os.path.exists(detail_path):
         os.remove(detail_path)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--cpu-budget", "1.5",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--cpu-budget", "1.5",
                         "--min-region-ms", "20", "--sustained-seconds", "3"], capture_output=True, text=True, timeout=1100, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -102,3 +104,41 @@ def test_bench_line_contract(built_libs):
         _check_roofline_full(o["roofline"], o["ms_per_step"], need_counters=False)
         _check_cpu_full(o["cpu_baseline"])
         assert o["value"] > 100 * o["cpu_baseline"]["all_cores"]["value"]
+
+
+def test_plain_run_times_exactly_the_steps_and_dumps_the_outputs(built_libs, tmp_path):
+    """Without --full: ONE region of exactly --steps timed steps and the headline's line only; --dump-outputs writes the records the
+    last timed step returned, which are what the same solver computes for the same seeded batch."""
+    import numpy as np
+    import torch
+    import quadruped_gait_generation_ismpc_amd as q
+    from quadruped_gait_generation_ismpc_amd import workload
+    dump = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype"):
+        assert k in d, k
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["regions"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert abs(d["region_ms_median"] - 7 * d["ms_per_step"]) <= 1e-3 * d["region_ms_median"]
+    assert abs(d["value"] - 65536 / (d["ms_per_step"] * 1e-3)) <= 1e-4 * d["value"]
+    for k in ("other_configs", "cpu_baseline", "sustained", "multi_gpu", "value_incl_pcie"):
+        assert k not in d, k
+    assert d["roofline"] is None
+    # the dumped records against the solver on the same inputs, in this process
+    names = set(q.TICK_OUT.names)
+    assert {f.name[:-4] for f in dump.iterdir()} == names
+    got = {n: np.load(dump / (n + ".npy")) for n in names}
+    assert all(a.dtype == np.float64 and a.shape[0] == 65536 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    p = q.default_params(N=100)
+    solver = q.MPCSolver(q.reference_plan(params=p), params=p, device=0)
+    exp = q.from_device(solver.solve_batch_torch(q.to_device(workload.make_batch(100, 65536), "cuda:0")), q.TICK_OUT)
+    torch.cuda.synchronize(); solver.close()
+    for n in ("status", "iters"):
+        assert (got[n] == exp[n].astype(np.float64)).all(), n
+    for n in ("com_pos", "com_vel", "u0"):
+        np.testing.assert_allclose(got[n], exp[n], rtol=1e-12, atol=1e-12, err_msg=n)
