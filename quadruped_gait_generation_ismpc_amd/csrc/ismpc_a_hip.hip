@@ -31,6 +31,8 @@
 #include <new>
 #include <algorithm>
 #include "ismpc_a_dev.hpp"
+#include "ismpc_wave_prims.hpp"
+#include "ismpc_host.hpp"
 
 namespace {
 
@@ -40,23 +42,7 @@ constexpr int MAXF = ismpc_a::MAXF;
 constexpr int QCAP = 264;              // capacity of the working set (>= C + F + 1)
 
 // ---- wave / block primitives ------------------------------------------------------------------
-template <int CTRL, int ROW_MASK, bool BOUND_ZERO>
-__device__ __forceinline__ double dpp64(double old, double src)
-{
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(src), CTRL, ROW_MASK, 0xf, BOUND_ZERO);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(src), CTRL, ROW_MASK, 0xf, BOUND_ZERO);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wave_scan_up(double v)   // inclusive prefix sum over the 64 lanes
-{
-    v += dpp64<0x111, 0xf, true>(0.0, v);
-    v += dpp64<0x112, 0xf, true>(0.0, v);
-    v += dpp64<0x114, 0xf, true>(0.0, v);
-    v += dpp64<0x118, 0xf, true>(0.0, v);
-    v += dpp64<0x142, 0xa, false>(0.0, v);
-    v += dpp64<0x143, 0xc, false>(0.0, v);
-    return v;
-}
+using ismpc_wave::wave_scan_up;       // inclusive prefix sum over the 64 lanes
 
 struct Shared {
     double u[T], zu[T], imp[T], zlo[T], zhi[T], w1[T], w2[T], a[T], PA[T + 1];
@@ -674,19 +660,12 @@ __global__ void ismpc_a_tick_prologue(const ismpc_a_state* __restrict__ state, i
     if (out) { out[i].status = 0; out[i].active = 0; out[i].iters_x = 0; out[i].iters_y = 0; }
 }
 
-struct DeviceGuardA {          // entry points leave the caller's current device as they found it
-    int prev = -1, dev; hipError_t err = hipSuccess;
-    explicit DeviceGuardA(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) err = hipSetDevice(dev);
-    }
-    ~DeviceGuardA() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-};
 thread_local std::string g_err_a = "";
 int fail_a(int code, const std::string& msg) { g_err_a = msg; return code; }
-#define HIP_TRY_A(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
-    return fail_a(-2, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
-#define ON_DEVICE_A(h_) DeviceGuardA guard_((h_)->device); HIP_TRY_A(guard_.err)
+#define HIP_TRY_A(expr) ISMPC_HIP_TRY(fail_a, expr)
+#define ON_DEVICE_A(h_) ISMPC_ON_DEVICE(fail_a, h_)
+using ismpc_host::grow_sync;
+using DeviceGuardA = ismpc_host::DeviceGuard;          // entry points leave the caller's current device as they found it
 
 // MATLAB linspace(d1, d2, n)
 void linspace_m(double d1, double d2, int n, std::vector<double>& y)
@@ -1054,15 +1033,8 @@ int ismpc_a_reserve(ismpc_a_handle* h, int max_batch)
     return 0;
 }
 
-// The handle's scratch (prev, hist, order, defer_list) outlives the call that allocated it and is used by later calls on
-// whatever stream those pass.  Before it is re-allocated on stream `s`, the previous launch's stream -- if it is another
-// one -- is drained: the free can then not overtake kernels that still use the block.
-static hipError_t grow_sync(ismpc_a_handle* h, hipStream_t s)
-{
-    if (h->used && h->last_stream != s) return hipStreamSynchronize(h->last_stream);
-    return hipSuccess;
-}
-
+// The handle's scratch (prev, pre, hist, order, defer_list) outlives the call that allocated it and is used by later calls on
+// whatever stream those pass: it grows through ISMPC_GROW_ASYNC (ismpc_host.hpp), which drains the previous launch's stream first.
 static int tick_launch(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, const ismpc_a_inst* inst_dev, const double* push_dev,
                        ismpc_a_out* out_dev, void* stream, int history = -1)
 {
@@ -1076,28 +1048,20 @@ static int tick_launch(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, c
     unsigned long long* hist = nullptr;
     if (history > 0) {
         if (batch > h->hist_cap) {                       // stream-ordered growth; ismpc_a_reserve sizes it beforehand
-            HIP_TRY_A(grow_sync(h, s)); if (h->hist) HIP_TRY_A(hipFreeAsync(h->hist, s));
-            h->hist = nullptr; h->hist_cap = 0; h->hist_valid = false;
-            HIP_TRY_A(hipMallocAsync((void**)&h->hist, sizeof(unsigned long long) * 16 * (size_t)batch, s));
-            h->hist_cap = batch;
+            h->hist_valid = false;
+            ISMPC_GROW_ASYNC(fail_a, h, h->hist, h->hist_cap, batch, sizeof(unsigned long long) * 16 * (size_t)batch, s);
         }
         hist = h->hist;
         if (history == 2 && !(h->hist_valid && h->hist_batch == batch)) history = 1;
         h->hist_valid = true; h->hist_batch = batch;
     }
     const int hist_load = history == 2 ? 1 : 0;
-    struct Mark { ismpc_a_handle* h; hipStream_t s; ~Mark() { h->last_stream = s; h->used = true; } } mark_{h, s};
+    ismpc_host::StreamMark<ismpc_a_handle> mark_{h, s};
     if (batch > h->prev_cap) {
-        HIP_TRY_A(grow_sync(h, s)); if (h->prev) HIP_TRY_A(hipFreeAsync(h->prev, s));
-        h->prev = nullptr; h->prev_cap = 0;
-        HIP_TRY_A(hipMallocAsync((void**)&h->prev, sizeof(ismpc_a_state) * (size_t)batch, s));
-        h->prev_cap = batch;
+        ISMPC_GROW_ASYNC(fail_a, h, h->prev, h->prev_cap, batch, sizeof(ismpc_a_state) * (size_t)batch, s);
     }
     if (inst_dev && batch > h->pre_cap) {
-        HIP_TRY_A(grow_sync(h, s)); if (h->pre) HIP_TRY_A(hipFreeAsync(h->pre, s));
-        h->pre = nullptr; h->pre_cap = 0;
-        HIP_TRY_A(hipMallocAsync((void**)&h->pre, sizeof(ismpc_a::PiPre) * (size_t)batch, s));
-        h->pre_cap = batch;
+        ISMPC_GROW_ASYNC(fail_a, h, h->pre, h->pre_cap, batch, sizeof(ismpc_a::PiPre) * (size_t)batch, s);
     }
     hipLaunchKernelGGL(ismpc_a_tick_prologue, dim3((batch + 255) / 256), dim3(256), 0, s, (const ismpc_a_state*)state_dev, h->prev, out_dev, batch,
                        (h->use_wave || inst_dev) ? h->work_counter : nullptr, inst_dev, inst_dev ? h->pre : nullptr, h->c.grav, h->c.dt, h->c.C, h->c.P);
@@ -1123,10 +1087,7 @@ static int tick_launch(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, c
         };
         if (inst_dev && h->c.F > 3 && h->bucket_by_F && rl <= 4 && h->c.F <= 6) {
             if (batch > h->order_cap) {
-                HIP_TRY_A(grow_sync(h, s)); if (h->order) HIP_TRY_A(hipFreeAsync(h->order, s));
-                h->order = nullptr; h->order_cap = 0;
-                HIP_TRY_A(hipMallocAsync((void**)&h->order, sizeof(int) * (4 * (size_t)batch + 4), s));
-                h->order_cap = batch;
+                ISMPC_GROW_ASYNC(fail_a, h, h->order, h->order_cap, batch, sizeof(int) * (4 * (size_t)batch + 4), s);
             }
             int* counts = h->order + 4 * (size_t)h->order_cap;
             HIP_TRY_A(hipMemsetAsync(counts, 0, 4 * sizeof(int), s));
@@ -1142,10 +1103,7 @@ static int tick_launch(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, c
             const bool resolve = h->precision == 1 && !h->defer_off;
             if (resolve) {
                 if (batch > h->defer_cap) {                  // stream-ordered growth, as the history
-                    HIP_TRY_A(grow_sync(h, s)); if (h->defer_list) HIP_TRY_A(hipFreeAsync(h->defer_list, s));
-                    h->defer_list = nullptr; h->defer_cap = 0;
-                    HIP_TRY_A(hipMallocAsync((void**)&h->defer_list, sizeof(int) * 2 * (size_t)batch, s));
-                    h->defer_cap = batch;
+                    ISMPC_GROW_ASYNC(fail_a, h, h->defer_list, h->defer_cap, batch, sizeof(int) * 2 * (size_t)batch, s);
                 }
                 WL.defer_list = h->defer_list; WL.defer_count = h->work_counter + 2;
             }

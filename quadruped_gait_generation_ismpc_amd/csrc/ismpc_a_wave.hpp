@@ -35,6 +35,7 @@
 #include <algorithm>
 #include <type_traits>
 #include "ismpc_a_dev.hpp"
+#include "ismpc_wave_prims.hpp"
 
 namespace ismpc_a {
 
@@ -73,30 +74,10 @@ template <> struct Num<float> {
 };
 
 // ---- wave primitives, both precisions -------------------------------------------------------------------------------------
-template <int CTRL, int ROW_MASK, bool BOUND_ZERO>
-__device__ __forceinline__ double dppv(double old, double src)
-{
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(src), CTRL, ROW_MASK, 0xf, BOUND_ZERO);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(src), CTRL, ROW_MASK, 0xf, BOUND_ZERO);
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL, int ROW_MASK, bool BOUND_ZERO>
-__device__ __forceinline__ float dppv(float old, float src)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src), CTRL, ROW_MASK, 0xf, BOUND_ZERO));
-}
+using ismpc_wave::dppv;               // DPP move, double and float (ismpc_wave_prims.hpp)
+using ismpc_wave::wave_scan_up;       // inclusive prefix sum over the 64 lanes
 template <int CTRL, int RM> __device__ __forceinline__ int dpp_i(int old, int v) { return __builtin_amdgcn_update_dpp(old, v, CTRL, RM, 0xf, false); }
 
-template <typename R> __device__ __forceinline__ R wave_scan_up(R v)       // inclusive prefix sum over the 64 lanes
-{
-    v += dppv<0x111, 0xf, true>(R(0), v);
-    v += dppv<0x112, 0xf, true>(R(0), v);
-    v += dppv<0x114, 0xf, true>(R(0), v);
-    v += dppv<0x118, 0xf, true>(R(0), v);
-    v += dppv<0x142, 0xa, false>(R(0), v);
-    v += dppv<0x143, 0xc, false>(R(0), v);
-    return v;
-}
 __device__ __forceinline__ double rl(double v, int l)
 {
     const int ll = __builtin_amdgcn_readfirstlane(l);

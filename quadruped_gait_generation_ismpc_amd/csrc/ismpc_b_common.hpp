@@ -1,0 +1,171 @@
+// Formulation B, part 1 of 4 of the translation unit ismpc_hip.hip (which sets the floating-point contraction for all parts):
+// what every kernel family shares -- the launch constants (DevConst), the caller bookkeeping in front of a tick (Walk,
+// load_walk, gate_tick), small device functions, the per-instance registers of the lane-group kernels (QState / QOut) with
+// their record stores, and the -DISMPC_STAMPS instrumentation.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include "ismpc_tables.hpp"
+#include "ismpc_wave_prims.hpp"
+
+namespace {
+
+using namespace ismpc_wave;
+
+struct DevConst {
+    int N, NP, NPs, S, F, nmid, npat, Fmax, rows, tick_divisor;
+    double dt, cdt, mass, g, h_des, half_run, half_first, q_p, q_u, q_v, z_lo, z_hi, gate, eta;
+    double inv_mass, dt_over_mass, inv_eta, sim_div, cdt_over_dt;   // 1/m, dt/m (B_z), 1/eta (C_sc), dt/cdt, cdt/dt: uniform divisions hoisted to the host
+    const double *Hinv, *W, *midx, *midy, *midz, *tailx, *taily, *ftsp_t;
+    const int *e_lo, *ne;
+    // affine form of the vertical stage (ismpc_tables.hpp)
+    const double *vtab, *tz, *tg, *dU, *SdU, *Wt, *SW;
+    int flat;
+    // inequality fallback (0 <= S u <= 1e4 active)
+    const double *HSt, *SHSt;
+    const DevConst* sets; int nsets;  // parameter sweeps (ismpc_create_sweep): one record per parameter set, its own tables and scalars; the
+                                      // instance's record names its set (ismpc_tick_in.reserved).  NULL / 0 for a plain handle
+    const int* order;                 // sweeps, after ismpc_sweep_bind: the instances of the bound batch sorted by parameter set.  Slot g of the
+                                      // launch runs instance order[g], so the lane groups of a wavefront read ONE set's tables, and workgroup b
+                                      // takes the slots of virtual block sweep_vblock(b): the workgroups an XCD receives (b mod 8) cover one
+                                      // contiguous eighth of the sorted batch -- K / 8 sets' tables per L2 instead of all K.  NULL: slot g = instance g
+    int* zflag;                       // four self-resetting counters (zeroed once, at ismpc_create): [0] entries in the deferred list of the
+                                      // running two-launch step, [1] fallback workgroups done with it, [2] instances an in-kernel rollout
+                                      // parked for its resume launch, [3] resume workgroups done.  The consumer launch exits at once on a
+                                      // zero count; otherwise its LAST workgroup zeroes the pair again -- so the counters are valid whatever
+                                      // launched before (a rollout between two ticks, hipGraph replays of one captured step: the count does
+                                      // not depend on launch ids and no memset sits outside a captured step)
+    int* zseen;                       // id of the last launch that deferred an instance, in a word of host memory (written, never read, by the device): how the host picks the launch form
+    double* zpool; int* zbusy;        // active-set fallback: slots of zstride doubles (G^-1 cap x cap + per-entry vectors), one lock word per slot
+    int zslots, zcap, zldsq; size_t zstride;   // zldsq: entries the fallback keeps in its LDS window before it moves to a slot (Z_LDS_Q; ISMPC_Z_LDS_Q lowers it: tests)
+    // sample-major copies for ismpc_tick_quad: a lane's R samples are one contiguous run (16-byte loads, one base address)
+    const double *vq;                 // (npat+1) x NT x 6 : U0,Ua,Ub,SU0,SUa,SUb per sample
+    const double *tzg;                // NT x 2 : tz, tg per sample
+    const double *midxy;              // nmid x 2 : midx, midy per sample
+    // the same tables laid out for the lane-group kernels' shape (R samples per lane, LPI lanes per instance), so that one
+    // wave-wide load instruction reads LPI x 16 contiguous bytes per instance (a lane's samples are NOT contiguous here):
+    const double *vqT;                // (npat+1) x R x 3 x LPI double2 : pair k of sample li*R + r at [((p R + r) 3 + k) LPI + li]
+    const double *tzgT;               // R x LPI double2 : (tz, tg) of sample li*R + r at [r LPI + li]
+};
+
+struct M2 { double a, b, c, d; };   // [a b; c d]
+__device__ __forceinline__ M2 mul(const M2& x, const M2& y)
+{
+    M2 r;
+    r.a = fma(x.a, y.a, x.b * y.c); r.b = fma(x.a, y.b, x.b * y.d);
+    r.c = fma(x.c, y.a, x.d * y.c); r.d = fma(x.c, y.b, x.d * y.d);
+    return r;
+}
+template <int LANE>
+__device__ __forceinline__ M2 readlane_m2(const M2& y)
+{
+    return (M2){readlane64<LANE>(y.a), readlane64<LANE>(y.b), readlane64<LANE>(y.c), readlane64<LANE>(y.d)};
+}
+
+// sinh(x)/x and (cosh(x)-1)/x^2 as functions of w = x^2.  Taylor to w^7 is exact to < 1 ulp for
+// w <= 0.25 (next term 4e-20); beyond that (lambda dt^2 > 0.25: never on a physical gait) libm.
+__device__ __forceinline__ void sinhc_coshc(double w, double& P, double& Q)
+{
+    if (__builtin_expect(w <= 0.25, 1)) {
+        P = 1.0 / 1307674368000.0;                 // 1/15!
+        P = fma(P, w, 1.0 / 6227020800.0);            // 1/13!
+        P = fma(P, w, 1.0 / 39916800.0);              // 1/11!
+        P = fma(P, w, 1.0 / 362880.0);                // 1/9!
+        P = fma(P, w, 1.0 / 5040.0);                  // 1/7!
+        P = fma(P, w, 1.0 / 120.0);                   // 1/5!
+        P = fma(P, w, 1.0 / 6.0);                     // 1/3!
+        P = fma(P, w, 1.0);
+        Q = 1.0 / 20922789888000.0;                // 1/16!
+        Q = fma(Q, w, 1.0 / 87178291200.0);           // 1/14!
+        Q = fma(Q, w, 1.0 / 479001600.0);             // 1/12!
+        Q = fma(Q, w, 1.0 / 3628800.0);               // 1/10!
+        Q = fma(Q, w, 1.0 / 40320.0);                 // 1/8!
+        Q = fma(Q, w, 1.0 / 720.0);                   // 1/6!
+        Q = fma(Q, w, 1.0 / 24.0);                    // 1/4!
+        Q = fma(Q, w, 0.5);
+    } else {
+        const double x = sqrt(w);
+        P = sinh(x) / x;
+        Q = (cosh(x) - 1.0) / w;
+    }
+}
+
+// Per-launch scratch of the inequality fallback of the two-launch form: the LIST of deferred instances (batch ints).  The per-tick
+// kernel appends an instance under the handle's counter DevConst::zflag[0]; the fallback launch behind it walks exactly those entries
+// (scanning 65 536 marks with 256 wavefronts cost 0.5 ms whenever anything was deferred) and its last workgroup zeroes the counter.
+__host__ __device__ inline size_t zscratch_bytes(int batch) { return 4 * (size_t)batch + 16; }
+__device__ __forceinline__ int* zlist_of(unsigned char* zmark, int) { return reinterpret_cast<int*>(zmark); }
+// Caller bookkeeping in front of solve(): Controller.cpp:297-304 (enabled) and :310.
+struct Walk { double sim; int mpc, ctl, fc; };
+__device__ __forceinline__ Walk load_walk(const DevConst& c, const ismpc_tick_in* rec, int rollout_frame)
+{
+    Walk w; w.sim = rec->simulation_time; w.mpc = rec->mpc_iter; w.ctl = rec->control_iter; w.fc = rec->footstep_counter;
+    if (rollout_frame >= 0) {
+        if (w.fc >= 0 && w.fc < c.rows && w.sim >= c.ftsp_t[w.fc] - 1) { w.ctl = 0; w.mpc = 0; w.fc = w.fc + 1; }
+        w.sim = (double)rollout_frame;
+    }
+    return w;
+}
+// 0 = run the tick, else the pass-through status (MPCSolver.cpp:214; index range of :259,381)
+__device__ __forceinline__ int gate_tick(const DevConst& c, const Walk& w, int& idx)
+{
+    idx = 0;
+    if ((w.ctl % c.tick_divisor) != 0) return ISMPC_ST_TICK_SKIPPED;
+    const double t = (c.sim_div == 1.0) ? w.sim : w.sim / c.sim_div;
+    if (!(t > -1.0) || !(t < 2.0e9)) return ISMPC_ST_BAD_INDEX;
+    idx = (int)t;
+    if (idx < 0 || idx + 2 * c.N > c.nmid || w.mpc < 0) return ISMPC_ST_BAD_INDEX;
+    return 0;
+}
+
+// 1/x to rounding error: v_rcp_f64 + two Newton steps (the IEEE division sequence is about three times as long)
+__device__ __forceinline__ double frcp(double x)
+{
+    double r = __builtin_amdgcn_rcp(x);
+    r = fma(fma(-x, r, 1.0), r, r);
+    r = fma(fma(-x, r, 1.0), r, r);
+    return r;
+}
+
+// -DISMPC_STAMPS (diagnostic build, scripts/stamps_b.py): wall-clock stamps (s_memrealtime, 100 MHz) of every wavefront of the
+// per-tick lane-group kernels at a few points of the tick; written to a buffer nothing else reads.
+#ifdef ISMPC_STAMPS
+__device__ unsigned long long g_stamps[16384 * 8];
+__device__ __forceinline__ unsigned long long stamp_now()
+{
+    unsigned long long t;
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+    return t;
+}
+#define STAMP(k_) do { if (g_stamp_wave >= 0 && g_stamp_wave < 16384) { const unsigned long long t_ = stamp_now(); if ((threadIdx.x & 63) == 0) g_stamps[g_stamp_wave * 8 + (k_)] = t_; } } while (0)
+#define STAMP_DECL const int g_stamp_wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)
+#else
+#define STAMP(k_) do {} while (0)
+#define STAMP_DECL do {} while (0)
+#endif
+
+// What one instance carries from tick to tick (group-uniform: every lane of the group holds the same values) and what a tick
+// produces (valid in lane 0 of the group).
+struct QState { double x, y, z, xd, yd, zd; Walk w; int ps; };     // ps: parameter set of the instance (sweep handles; -1 = invalid record)
+struct QOut { double x, y, z, xd, yd, zd, uz0, ux0, uy0; int status, itx, ity; };
+
+__device__ __forceinline__ void store_record(ismpc_tick_out* __restrict__ rec, const QOut& o)
+{
+    double2* o2 = reinterpret_cast<double2*>(rec);
+    const long long packed = (long long)(unsigned)o.status | ((long long)(unsigned)((o.itx & 255) | ((o.ity & 255) << 8)) << 32);
+    o2[0] = make_double2(o.x, o.y); o2[1] = make_double2(o.z, o.xd); o2[2] = make_double2(o.yd, o.zd);
+    o2[3] = make_double2(o.uz0, o.ux0); o2[4] = make_double2(o.uy0, __longlong_as_double(packed));
+}
+// Controller.cpp:346-348 (feed the output back), :503-504 (advance the counters)
+__device__ __forceinline__ void store_feedback(const DevConst& c, ismpc_tick_in* __restrict__ st, const QOut& o, const Walk& w)
+{
+    st->com_pos[0] = o.x; st->com_pos[1] = o.y; st->com_pos[2] = o.z;
+    st->com_vel[0] = o.xd; st->com_vel[1] = o.yd; st->com_vel[2] = o.zd;
+    st->simulation_time = w.sim;
+    const int ctl = w.ctl + 1;
+    st->control_iter = ctl;
+    st->mpc_iter = (int)floor(ctl * c.cdt / c.dt);     // as written at Controller.cpp:504 (see tick_affine_body)
+    st->footstep_counter = w.fc;
+}
+
+}  // namespace

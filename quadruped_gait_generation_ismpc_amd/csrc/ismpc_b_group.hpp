@@ -1,0 +1,725 @@
+// Formulation B, part 4 of 4 of the translation unit ismpc_hip.hip: the lane-group family, the default for horizons N <= 128.
+// Per-tick kernels ismpc_tick_quad (two-launch form, with ismpc_tick_affine_fallback behind it), ismpc_tick_quad_inline and
+// ismpc_tick_quad_one (one launch per step), the closed loop inside one launch (ismpc_rollout_quad), and the counting sort of
+// ismpc_sweep_bind (sweep_sort_*).
+#pragma once
+#include "ismpc_b_affine.hpp"
+
+namespace {
+
+// =====================================================================================================================
+// SEVERAL instances per wavefront, one group of LPI lanes each (horizons N <= 128): LPI = 16 (a DPP row, four instances per
+// wavefront) or LPI = 8 (half a row, eight instances).  A horizon of 100 samples fills only 100 of the 128 sample slots of a
+// wavefront and, worse, every scan, reduction and scalar of the tick is paid once per wavefront: with one instance per lane
+// group the R = ceil(N/LPI) samples a lane owns are independent work for the FP64 pipe, the scans / reductions are log2(LPI)
+// DPP steps inside a group (no cross-row fold, no readlane), and what used to be wave-uniform is group-uniform.  Same
+// arithmetic as tick_affine_body; instances whose vertical QP has active inequality rows are deferred exactly as there.
+template <int CTRL, int BANK_MASK>
+__device__ __forceinline__ double dpp64b(double old, double src)
+{
+    const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(src), CTRL, 0xf, BANK_MASK, false);
+    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(src), CTRL, 0xf, BANK_MASK, false);
+    return __hiloint2double(hi, lo);
+}
+// DPP move that writes every lane (rotations; shifts with bound_ctrl): no "old" operand, so no register to pre-load
+template <int CTRL, bool BOUND_ZERO>
+__device__ __forceinline__ double dpp64n(double src)
+{
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(src), CTRL, 0xf, 0xf, BOUND_ZERO);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(src), CTRL, 0xf, 0xf, BOUND_ZERO);
+    return __hiloint2double(hi, lo);
+}
+// Lane-group primitives.  LPI = 16: the group is a DPP row.  LPI = 8: two groups per row; a shift by 4 is confined to its
+// half row with the bank mask (banks 1 and 3 keep the zero / the old value), shifts by 1 and 2 zero the lanes whose source
+// sits in the neighbouring group; sums are xor butterflies (quad_perm, quad_perm, row_half_mirror).
+template <int LPI> struct Grp;
+template <> struct Grp<16> {
+    static constexpr int STEPS = 4;
+    __device__ static __forceinline__ double sum(double v)             // sum over the group, in every lane (row_ror:1,2,4,8)
+    {
+        v += dpp64n<0x121, false>(v); v += dpp64n<0x122, false>(v); v += dpp64n<0x124, false>(v); v += dpp64n<0x128, false>(v);
+        return v;
+    }
+    __device__ static __forceinline__ int sum_i(int v)
+    {
+        v += __builtin_amdgcn_mov_dpp(v, 0x121, 0xf, 0xf, false); v += __builtin_amdgcn_mov_dpp(v, 0x122, 0xf, 0xf, false);
+        v += __builtin_amdgcn_mov_dpp(v, 0x124, 0xf, 0xf, false); v += __builtin_amdgcn_mov_dpp(v, 0x128, 0xf, 0xf, false);
+        return v;
+    }
+    // v from lane + 2^K of the group, 0 past its end
+    template <int K> __device__ static __forceinline__ double shl0(double v, int) { return dpp64n<0x100 + (1 << K), true>(v); }
+    // lane 0 of the group, in every lane: quad_perm [0,0,0,0], then row_shr:4 into bank 1, row_shr:8 into banks 2,3
+    __device__ static __forceinline__ double bcast0(double v)
+    {
+        v = dpp64b<0x000, 0xf>(v, v); v = dpp64b<0x114, 0x2>(v, v); v = dpp64b<0x118, 0xc>(v, v);
+        return v;
+    }
+    // v from the next lane of the group; the last lane gets `fill`
+    __device__ static __forceinline__ double next_or(double fill, double v, int) { return dppv<0x101, 0xf, false>(fill, v); }
+};
+// LPI = 32: two rows per group (two instances per wavefront; R = 4 samples per lane at N <= 128).  Row-local DPP steps as for
+// 16, one exchange with the partner row (lane ^ 16: ds_swizzle) for the sums, readlane of lanes 16 / 48 for the scan's fifth step.
+__device__ __forceinline__ double swz16(double v)       // the value of lane ^ 16
+{
+    return __hiloint2double(__builtin_amdgcn_ds_swizzle(__double2hiint(v), 0x401F), __builtin_amdgcn_ds_swizzle(__double2loint(v), 0x401F));
+}
+template <> struct Grp<32> {
+    static constexpr int STEPS = 5;
+    __device__ static __forceinline__ double sum(double v)
+    {
+        v += dpp64n<0x121, false>(v); v += dpp64n<0x122, false>(v); v += dpp64n<0x124, false>(v); v += dpp64n<0x128, false>(v);
+        return v + swz16(v);
+    }
+    __device__ static __forceinline__ int sum_i(int v)
+    {
+        v += __builtin_amdgcn_mov_dpp(v, 0x121, 0xf, 0xf, false); v += __builtin_amdgcn_mov_dpp(v, 0x122, 0xf, 0xf, false);
+        v += __builtin_amdgcn_mov_dpp(v, 0x124, 0xf, 0xf, false); v += __builtin_amdgcn_mov_dpp(v, 0x128, 0xf, 0xf, false);
+        return v + __builtin_amdgcn_ds_swizzle(v, 0x401F);
+    }
+    // steps 0-3 stay inside a row (v from lane + 2^K of the ROW, 0 past its end); step 4 is grp_scan_step's own
+    template <int K> __device__ static __forceinline__ double shl0(double v, int) { return dpp64n<0x100 + (1 << K), true>(v); }
+    __device__ static __forceinline__ double bcast0(double v)
+    {
+        const double a = readlane64<0>(v), b = readlane64<32>(v);
+        return ((threadIdx.x & 32) != 0) ? b : a;
+    }
+    // v from the next lane of the group (wave_shl:1 crosses the row boundary); the last lane gets `fill`
+    __device__ static __forceinline__ double next_or(double fill, double v, int li)
+    {
+        const double t = dppv<0x130, 0xf, false>(fill, v);
+        return (li == 31) ? fill : t;
+    }
+};
+template <> struct Grp<8> {
+    static constexpr int STEPS = 3;
+    __device__ static __forceinline__ double sum(double v)
+    {
+        v += dpp64n<0x0B1, false>(v);                                  // quad_perm [1,0,3,2]
+        v += dpp64n<0x04E, false>(v);                                  // quad_perm [2,3,0,1]
+        v += dpp64n<0x141, false>(v);                                  // row_half_mirror: lane l <-> 7 - l of its half row
+        return v;
+    }
+    __device__ static __forceinline__ int sum_i(int v)
+    {
+        v += __builtin_amdgcn_mov_dpp(v, 0x0B1, 0xf, 0xf, false); v += __builtin_amdgcn_mov_dpp(v, 0x04E, 0xf, 0xf, false);
+        v += __builtin_amdgcn_mov_dpp(v, 0x141, 0xf, 0xf, false);
+        return v;
+    }
+    template <int K> __device__ static __forceinline__ double shl0(double v, int li)
+    {
+        if constexpr (K == 2) return dpp64b<0x104, 0x5>(0.0, v);      // banks 0 and 2 read lanes + 4; banks 1 and 3 stay 0
+        else { const double t = dpp64n<0x100 + (1 << K), true>(v); return (li + (1 << K) < 8) ? t : 0.0; }
+    }
+    __device__ static __forceinline__ double bcast0(double v)
+    {
+        v = dpp64b<0x000, 0xf>(v, v); v = dpp64b<0x114, 0xa>(v, v);    // quad_perm [0,0,0,0]; banks 1,3 <- banks 0,2
+        return v;
+    }
+    __device__ static __forceinline__ double next_or(double fill, double v, int li)
+    {
+        const double t = dppv<0x101, 0xf, false>(fill, v);
+        return (li == 7) ? fill : t;
+    }
+};
+// y <- T y for T = I + Tm taken from lane + 2^K of the group (Tm = 0 past the end of the group)
+template <int LPI, int K>
+__device__ __forceinline__ void grp_scan_step(M2& y, int li)
+{
+    if constexpr (LPI == 32 && K == 4) {
+        // the rows have their own suffix products; the lower row of a group still needs the upper row's total (its lane 16 / 48)
+        const bool g1 = (threadIdx.x & 32) != 0, low = li < 16;
+        const double ya = g1 ? readlane64<48>(y.a) : readlane64<16>(y.a), yb = g1 ? readlane64<48>(y.b) : readlane64<16>(y.b);
+        const double yc = g1 ? readlane64<48>(y.c) : readlane64<16>(y.c), yd = g1 ? readlane64<48>(y.d) : readlane64<16>(y.d);
+        const double ta = low ? ya - 1.0 : 0.0, tb = low ? yb : 0.0, tc = low ? yc : 0.0, td = low ? yd - 1.0 : 0.0;
+        M2 r;
+        r.a = fma(ta, y.a, fma(tb, y.c, y.a)); r.b = fma(ta, y.b, fma(tb, y.d, y.b));
+        r.c = fma(tc, y.a, fma(td, y.c, y.c)); r.d = fma(tc, y.b, fma(td, y.d, y.d));
+        y = r;
+    } else
+    if constexpr (K < Grp<LPI>::STEPS) {
+        const double ta = Grp<LPI>::template shl0<K>(y.a - 1.0, li), tb = Grp<LPI>::template shl0<K>(y.b, li);
+        const double tc = Grp<LPI>::template shl0<K>(y.c, li), td = Grp<LPI>::template shl0<K>(y.d - 1.0, li);
+        M2 r;
+        r.a = fma(ta, y.a, fma(tb, y.c, y.a)); r.b = fma(ta, y.b, fma(tb, y.d, y.b));
+        r.c = fma(tc, y.a, fma(td, y.c, y.c)); r.d = fma(tc, y.b, fma(td, y.d, y.d));
+        y = r;
+    }
+}
+
+// One tick of one instance per lane group, registers in, registers out.  `s.w` is the WalkState the tick runs with (caller
+// bookkeeping already applied).  Returns true in every lane of a group whose instance has active vertical inequality rows
+// (deferred to the active-set fallback; its QOut is then provisional).
+// LDS of one wavefront of the lane-group kernels: the midpoint window of each of its instances, staged so that the global
+// loads are coalesced (lane li reads sample k LPI + li) and every lane then picks up its own R consecutive samples.  A lane's
+// block starts at li * MIDM double2; MIDM is odd, which keeps the 16-byte reads of 16 lanes on 16 different bank quads.
+template <int R> constexpr int midm() { return R | 1; }
+template <int R, int LPI> constexpr int wave_lds_double2() { return (64 / LPI) * LPI * midm<R>(); }
+// ... and, in the kernels that run the inequality fallback themselves, at least the fallback's working window (z_active_set)
+template <int R, int LPI> constexpr int wave_lds_double2_fb() { return wave_lds_double2<R, LPI>() > (Z_LDS_DOUBLES + 1) / 2 ? wave_lds_double2<R, LPI>() : (Z_LDS_DOUBLES + 1) / 2; }
+
+// KF: how the knapsack Newton loop is scheduled, not what it computes (the iterates are bit-identical): 0 = count the saturated
+// samples first and form the two sums only for axes that still move (fewest instructions: batches that fill the chip are
+// VALU-issue bound); 1 = count and sums of both axes in one pass, six interleaved group reductions instead of up to three
+// dependent ones per axis.  Measured (scripts/kf_sweep.sh, MI355X): 1 is slower at every batch size -- 10.2 vs 9.7 us at 1 024
+// instances, 14.0 vs 12.8 at 8 192, 51.8 vs 46.7 at 65 536, 5.9 vs 5.4 us per tick in the rollout kernel -- even one wavefront
+// alone on its SIMD is bound by the number of instructions it issues, not by the reduction chains.  Kept as a build-time knob.
+#ifndef ISMPC_KF_INLINE
+#define ISMPC_KF_INLINE 0
+#endif
+#ifndef ISMPC_KF_MAIN
+#define ISMPC_KF_MAIN 0
+#endif
+#ifndef ISMPC_KF_ROLLOUT
+#define ISMPC_KF_ROLLOUT 0
+#endif
+// SW: parameter sweep -- the groups of a wavefront may belong to different parameter sets: what depends on the set (tables
+// of the vertical stage, tails, mass, eta, box widths, bounds on S u) is read through the instance's own record c.sets[s.ps]
+// (per-lane loads); horizon, plan, dt, g and the gate are the handle's.  SW = false compiles to exactly the plain kernel.
+template <int R, int LPI, int KF, bool SW = false>
+__device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lane, const QState& s, QOut& o, double* __restrict__ u_traj_inst,
+                                                double2* __restrict__ lds_wave)
+{
+    constexpr int NT = ismpc::Tables::NT;
+    const int N = c.N;
+    const int li = lane & (LPI - 1);                  // lane inside the group = inside the instance
+    const double dt = c.dt;
+    const Walk& w = s.w;
+    const double x0 = s.x, y0 = s.y, z0 = s.z, xd0 = s.xd, yd0 = s.yd, zd0 = s.zd;
+    const DevConst* P = SW ? c.sets + (s.ps >= 0 ? s.ps : 0) : nullptr;
+    const double* p_vqT = SW ? P->vqT : c.vqT;
+    const double p_z_lo = SW ? P->z_lo : c.z_lo, p_z_hi = SW ? P->z_hi : c.z_hi;
+    const double p_inv_mass = SW ? P->inv_mass : c.inv_mass, p_inv_eta = SW ? P->inv_eta : c.inv_eta;
+    const double p_half_run = SW ? P->half_run : c.half_run, p_half_first = SW ? P->half_first : c.half_first;
+    const double* p_tailx = SW ? P->tailx : c.tailx; const double* p_taily = SW ? P->taily : c.taily;
+    const double p_dt_over_mass = SW ? P->dt_over_mass : c.dt_over_mass, p_h_des = SW ? P->h_des : c.h_des;
+    int idx;
+    const int gate_status = gate_tick(c, w, idx) | ((SW && s.ps < 0) ? ISMPC_ST_BAD_INDEX : 0);     // group-uniform; a gated group runs the arithmetic on idx = 0 and drops it
+    int status = gate_status;
+    const bool run = gate_status == 0;
+    if (!run) idx = 0;
+    const int n0 = li * R;                            // this lane owns samples n0 .. n0+R-1 (tables are zero past N)
+    STAMP_DECL;
+    STAMP(1);                                         // the record has arrived (gate_tick consumed it)
+
+    // ---- vertical stage from the affine tables (MPCSolver.cpp:223-243, is_running :262-263)
+    const int pat = (run && w.fc > 1 && w.mpc < c.npat) ? w.mpc : c.npat;
+    const double2* T = reinterpret_cast<const double2*>(p_vqT) + (size_t)pat * (R * 3 * LPI) + li;  // 3 x 16 bytes per sample, lane-contiguous
+    // midpoint window [idx, idx + LPI R) of this instance -> LDS, coalesced (consumed after the scan; MPCSolver.cpp:328-338,388-389)
+    constexpr int MIDM = midm<R>();
+    double2* Lm = lds_wave + (lane / LPI) * (LPI * MIDM);
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        const int j = k * LPI + li;
+        Lm[(j / R) * MIDM + (j % R)] = reinterpret_cast<const double2*>(c.midxy)[min(idx + j, c.nmid - 1)];
+    }
+    double u[R], su[R];
+    double smin = INFINITY, smax = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const double2 t01 = T[(3 * r) * LPI], t23 = T[(3 * r + 1) * LPI], t45 = T[(3 * r + 2) * LPI];
+        u[r] = fma(zd0, t23.x, fma(z0, t01.y, t01.x));
+        su[r] = fma(zd0, t45.y, fma(z0, t45.x, t23.y));
+        if (n0 + r < N) { smin = fmin(smin, su[r]); smax = fmax(smax, su[r]); }
+    }
+    if (!c.flat) {                                      // plans with mid_z != 0 (MPCSolver.cpp:259): per-frame offsets, pattern corrections
+        int elo = 0, ne = 0;
+        if (pat < c.npat) { elo = c.e_lo[pat]; ne = c.ne[pat]; }
+        const int pp = pat < c.npat ? pat : 0;
+        int nemax = 0;
+#pragma unroll
+        for (int g = 0; g < 64; g += LPI) nemax = max(nemax, __builtin_amdgcn_readlane(ne, g));
+        const double* dUr = (SW ? P->dU : c.dU) + (size_t)idx * NT;          // (a sweep: this instance's set has its own offsets and corrections)
+        const double* sUr = (SW ? P->SdU : c.SdU) + (size_t)idx * NT;
+        double du[R], ds[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) { du[r] = dUr[n0 + r]; ds[r] = sUr[n0 + r]; }
+        for (int e = 0; e < nemax; ++e) {
+            const bool on = e < ne;
+            const double ue = on ? dUr[elo + e] : 0.0;
+            const double* wr = (SW ? P->Wt : c.Wt) + ((size_t)pp * c.Fmax + (on ? e : 0)) * NT + n0;
+            const double* sr = (SW ? P->SW : c.SW) + ((size_t)pp * c.Fmax + (on ? e : 0)) * NT + n0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) { du[r] = fma(-wr[r], ue, du[r]); ds[r] = fma(-sr[r], ue, ds[r]); }
+        }
+        smin = INFINITY; smax = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int n = n0 + r;
+            u[r] += du[r]; su[r] += ds[r];
+            if (n >= elo && n < elo + ne) u[r] = 0.0;
+            if (n < N) { smin = fmin(smin, su[r]); smax = fmax(smax, su[r]); }
+        }
+    }
+    const double zlo_t = p_z_lo - 1e-11 * fmax(1.0, fabs(p_z_lo)), zhi_t = p_z_hi + 1e-11 * fmax(1.0, fabs(p_z_hi));
+    const bool viol = smin < zlo_t || smax > zhi_t;                                                // MPCSolver.cpp:158-160, beyond rounding
+    const unsigned long long vmask = __builtin_amdgcn_ballot_w64(viol);
+    const bool deferred = run && (((vmask >> (lane & (64 - LPI))) & ((1ull << LPI) - 1ull)) != 0ull);
+    if (deferred) status |= ISMPC_ST_Z_INEQ_ACTIVE;
+
+    // ---- lambda_j (MPCSolver.cpp:306) and A_j, B_j (:353-361): A = [1+wQ, dt P; lam dt P, 1+wQ], B = [-wQ, -lam dt P]
+    double ch1[R], s1[R], s2[R], lam0_l = 0.0;
+    bool big = false, mid = false;
+    {
+        double wv_[R], le_[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const double2 tq = reinterpret_cast<const double2*>(c.tzgT)[r * LPI + li];
+            const double zpos = su[r] + fma(tq.x, zd0, z0) + tq.y;                  // S u + T_bar_z s + T_bar_g_z
+            const double zacc = fma(p_inv_mass, u[r], -c.g);
+            const double lam = (c.g + zacc) * frcp(zpos);
+            if (r == 0) lam0_l = lam;
+            le_[r] = (lam < c.gate) ? 0.0 : lam;
+            const double dtn = (n0 + r < N) ? dt : 0.0;
+            wv_[r] = le_[r] * dtn * dtn;
+            s1[r] = dtn;                                  // dt_n for now
+            big = big || (wv_[r] > 0.25);
+            mid = mid || (wv_[r] > 0.004);
+        }
+        if (__builtin_amdgcn_ballot_w64(mid) == 0) {      // degree 3 is exact to < 1 ulp for w <= 0.004 (see tick_affine_body)
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double wv = wv_[r];
+                double P = 1.0 / 5040.0, Q = 1.0 / 40320.0;
+                P = fma(P, wv, 1.0 / 120.0);         Q = fma(Q, wv, 1.0 / 720.0);
+                P = fma(P, wv, 1.0 / 6.0);           Q = fma(Q, wv, 1.0 / 24.0);
+                P = fma(P, wv, 1.0);                 Q = fma(Q, wv, 0.5);
+                ch1[r] = wv * Q; s1[r] = s1[r] * P; s2[r] = le_[r] * s1[r];
+            }
+        } else {
+            // some group of this wavefront needs the long polynomial.  The choice is made PER GROUP (= per instance): a group whose own
+            // samples all have w <= 0.004 takes the degree-3 values here too, so an instance's record does not depend on which instances
+            // share its wavefront (round 4: a sweep sorted by parameter set, ismpc_sweep_bind, changes an instance's wave-mates)
+            const bool gmid = ((__builtin_amdgcn_ballot_w64(mid) >> (lane & (64 - LPI))) & ((LPI == 64) ? ~0ull : ((1ull << LPI) - 1ull))) != 0ull;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double wv = wv_[r], dtn = s1[r];
+                double P = 1.0 / 1307674368000.0, Q = 1.0 / 20922789888000.0;
+                P = fma(P, wv, 1.0 / 6227020800.0);  Q = fma(Q, wv, 1.0 / 87178291200.0);
+                P = fma(P, wv, 1.0 / 39916800.0);    Q = fma(Q, wv, 1.0 / 479001600.0);
+                P = fma(P, wv, 1.0 / 362880.0);      Q = fma(Q, wv, 1.0 / 3628800.0);
+                P = gmid ? fma(P, wv, 1.0 / 5040.0) : 1.0 / 5040.0;   Q = gmid ? fma(Q, wv, 1.0 / 40320.0) : 1.0 / 40320.0;   // (degree 3 starts here)
+                P = fma(P, wv, 1.0 / 120.0);         Q = fma(Q, wv, 1.0 / 720.0);
+                P = fma(P, wv, 1.0 / 6.0);           Q = fma(Q, wv, 1.0 / 24.0);
+                P = fma(P, wv, 1.0);                 Q = fma(Q, wv, 0.5);
+                ch1[r] = wv * Q; s1[r] = dtn * P; s2[r] = le_[r] * s1[r];
+                if (__builtin_amdgcn_ballot_w64(big) != 0 && wv > 0.25) {     // lambda dt^2 > 1/4: off any physical gait; libm
+                    const double x = sqrt(wv);
+                    ch1[r] = cosh(x) - 1.0; s1[r] = dtn * (sinh(x) / x); s2[r] = le_[r] * s1[r];
+                }
+            }
+        }
+    }
+    // ---- inclusive suffix product over the group: Y_l = A(block LPI-1) ... A(block l); C_sc = [1, 1/eta]
+    M2 Y = (M2){1.0 + ch1[0], s1[0], s2[0], 1.0 + ch1[0]};
+#pragma unroll
+    for (int r = 1; r < R; ++r) Y = mul((M2){1.0 + ch1[r], s1[r], s2[r], 1.0 + ch1[r]}, Y);
+    STAMP(2);                                         // tables arrived, lambda / A_j / local products done
+    grp_scan_step<LPI, 0>(Y, li); grp_scan_step<LPI, 1>(Y, li); grp_scan_step<LPI, 2>(Y, li); grp_scan_step<LPI, 3>(Y, li);
+    grp_scan_step<LPI, 4>(Y, li);
+    const double ie = p_inv_eta;
+    const double cva = fma(ie, Y.c, Y.a), cvb = fma(ie, Y.d, Y.b);       // C_sc (suffix product from this lane's first sample)
+    double c0 = Grp<LPI>::next_or(1.0, cva, li), c1 = Grp<LPI>::next_or(ie, cvb, li);                 // the lane needs it one lane up
+    // ---- Aeq(n) = C_sc phi_input(:,n) = c_n B_n, walking the lane's samples backwards
+    double a[R];
+#pragma unroll
+    for (int r = R - 1; r >= 0; --r) {
+        a[r] = -fma(c0, ch1[r], c1 * s2[r]);
+        const double k0 = fma(c0, ch1[r], fma(c1, s2[r], c0)), k1 = fma(c1, ch1[r], fma(c0, s1[r], c1));
+        c0 = k0; c1 = k1;
+    }
+    const double h = (w.fc > 1) ? p_half_run : p_half_first;                                          // MPCSolver.cpp:328-338
+    double q0 = 0.0, s_ax = 0.0, s_ay = 0.0, mx0 = 0.0, my0 = 0.0;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();          // the staged window is complete
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int n = n0 + r;
+        const double2 mq = Lm[li * MIDM + r];
+        const double mx = (n < N) ? mq.x : 0.0, my = (n < N) ? mq.y : 0.0;
+        if (r == 0) { mx0 = mx; my0 = my; }
+        q0 = fma(a[r], a[r], q0); s_ax = fma(a[r], mx, s_ax); s_ay = fma(a[r], my, s_ay);
+    }
+    q0 = Grp<LPI>::sum(q0); s_ax = Grp<LPI>::sum(s_ax); s_ay = Grp<LPI>::sum(s_ay);
+    // C_sc phi_state sits in lane 0 of the group (cva, cvb there); beq - a'mid (MPCSolver.cpp:381-384), group-uniform
+    const double bpx = Grp<LPI>::bcast0((p_tailx[idx] - fma(cva, x0, cvb * xd0)) - s_ax);
+    const double bpy = Grp<LPI>::bcast0((p_taily[idx] - fma(cva, y0, cvb * yd0)) - s_ay);
+    const double sgx = (bpx < 0.0) ? -1.0 : 1.0, sgy = (bpy < 0.0) ? -1.0 : 1.0;
+    STAMP(3);                                         // scan, backward walk, midpoints, reductions done
+    // min 1/2|v|^2, a'v = bp, |v| <= h  ->  v_n = sg sign(a_n) min(tau |a_n|, h): Newton on the concave piecewise-linear
+    // G(tau) = sum |a_n| min(tau |a_n|, h) from tau = 0; the groups iterate in lockstep, each with its own state
+    const double Tq[2] = { fabs(bpx), fabs(bpy) };
+    const double iq0 = frcp(q0);
+    double tau[2] = { Tq[0] * iq0, Tq[1] * iq0 };
+    int its[2] = {1, 1}, prev[2] = {0, 0};
+    bool live[2] = {true, true};
+    int st3 = 0;
+    if (!(q0 > 0.0)) {                                                       // no sample can move the ZMP
+#pragma unroll
+        for (int ax = 0; ax < 2; ++ax) {
+            tau[ax] = (Tq[ax] > 0.0) ? INFINITY : 0.0;
+            if (Tq[ax] > 1e-300) st3 |= (ax == 0 ? ISMPC_ST_X_INFEASIBLE : ISMPC_ST_Y_INFEASIBLE);
+        }
+    }
+    if constexpr (KF == 0) {
+        for (int it = 0; it < N + 2; ++it) {
+            if (__builtin_amdgcn_ballot_w64(live[0] || live[1]) == 0ull) break;
+#pragma unroll
+            for (int ax = 0; ax < 2; ++ax) {
+                if (__builtin_amdgcn_ballot_w64(live[ax]) == 0ull) continue;      // this axis is done in every group of the wavefront (the other one
+                                                                                  // keeps the loop alive for 0.6 more rounds on average: scripts/knapsack_hist.py)
+                int cl = 0;
+#pragma unroll
+                for (int r = 0; r < R; ++r) cl += (tau[ax] * fabs(a[r]) >= h) ? 1 : 0;
+                const int cnt = Grp<LPI>::sum_i(cl);
+                if (live[ax] && cnt == prev[ax]) live[ax] = false;                // active set unchanged: exact
+                if (__builtin_amdgcn_ballot_w64(live[ax]) == 0ull) continue;
+                double ssat = 0.0, qfree = 0.0;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    // 0 / 1 masks and two fused multiply-adds instead of two 64-bit selects and two adds: the same sums bit for bit
+                    // (fma(1, x, s) = s + x rounded once, fma(0, x, s) = s), a third fewer instructions in the loop the kernel spends most in
+                    const double ab = fabs(a[r]);
+                    const bool sat = tau[ax] * ab >= h;
+                    const double ms = sat ? 1.0 : 0.0, mf = sat ? 0.0 : 1.0;
+                    ssat = fma(ms, ab, ssat); qfree = fma(mf, a[r] * a[r], qfree);
+                }
+                ssat = Grp<LPI>::sum(ssat); qfree = Grp<LPI>::sum(qfree);
+                if (live[ax]) {
+                    ++its[ax];
+                    const double rem = fma(-h, ssat, Tq[ax]);
+                    if (!(qfree > 0.0)) {                                         // everything saturated
+                        if (rem > fma(h * ssat, 1e-12, 1e-300)) st3 |= (ax == 0 ? ISMPC_ST_X_INFEASIBLE : ISMPC_ST_Y_INFEASIBLE);
+                        tau[ax] = INFINITY; live[ax] = false;
+                    } else {
+                        const double tn = rem * frcp(qfree);
+                        if (!(tn > tau[ax])) live[ax] = false;
+                        else { tau[ax] = tn; prev[ax] = cnt; }
+                    }
+                }
+            }
+        }
+    } else {
+        for (int it = 0; it < N + 2; ++it) {
+            if (__builtin_amdgcn_ballot_w64(live[0] || live[1]) == 0ull) break;
+            int cl[2] = {0, 0};
+            double ssat[2] = {0.0, 0.0}, qfree[2] = {0.0, 0.0};
+#pragma unroll
+            for (int ax = 0; ax < 2; ++ax) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const bool sat = tau[ax] * fabs(a[r]) >= h;
+                    cl[ax] += sat ? 1 : 0; ssat[ax] += sat ? fabs(a[r]) : 0.0;
+                    const double a2 = a[r] * a[r]; qfree[ax] += sat ? 0.0 : a2;
+                }
+            }
+            const int cnt0 = Grp<LPI>::sum_i(cl[0]), cnt1 = Grp<LPI>::sum_i(cl[1]);
+            ssat[0] = Grp<LPI>::sum(ssat[0]); ssat[1] = Grp<LPI>::sum(ssat[1]);
+            qfree[0] = Grp<LPI>::sum(qfree[0]); qfree[1] = Grp<LPI>::sum(qfree[1]);
+#pragma unroll
+            for (int ax = 0; ax < 2; ++ax) {
+                const int cnt = ax == 0 ? cnt0 : cnt1;
+                if (live[ax] && cnt == prev[ax]) live[ax] = false;            // active set unchanged: exact
+                if (live[ax]) {
+                    ++its[ax];
+                    const double rem = fma(-h, ssat[ax], Tq[ax]);
+                    if (!(qfree[ax] > 0.0)) {                                 // everything saturated
+                        if (rem > fma(h * ssat[ax], 1e-12, 1e-300)) st3 |= (ax == 0 ? ISMPC_ST_X_INFEASIBLE : ISMPC_ST_Y_INFEASIBLE);
+                        tau[ax] = INFINITY; live[ax] = false;
+                    } else {
+                        const double tn = rem * frcp(qfree[ax]);
+                        if (!(tn > tau[ax])) live[ax] = false;
+                        else { tau[ax] = tn; prev[ax] = cnt; }
+                    }
+                }
+            }
+        }
+    }
+
+    STAMP(4);                                         // knapsack Newton done
+    // ---- lane 0 of the group finishes the instance: integration (MPCSolver.cpp:274-278, 406-422)
+    o.x = x0; o.y = y0; o.z = z0; o.xd = xd0; o.yd = yd0; o.zd = zd0;
+    o.uz0 = 0.0; o.ux0 = 0.0; o.uy0 = 0.0; o.itx = 0; o.ity = 0;
+    if (li == 0 && run) {
+        o.uz0 = u[0];
+        o.z = fma(dt, zd0, z0);
+        o.zd = fma(p_dt_over_mass, o.uz0, zd0) - dt * c.g;
+        if (isnan(o.z)) { o.z = p_h_des; status |= ISMPC_ST_Z_NAN; }
+        if (isnan(o.zd)) { o.zd = 0.0; status |= ISMPC_ST_Z_NAN; }
+        const double A0a = 1.0 + ch1[0], A0b = s1[0], A0c = s2[0];
+        if (lam0_l > c.gate) {                                            // MPCSolver.cpp:322
+            status |= st3; o.itx = its[0]; o.ity = its[1];
+            const double sa0 = (a[0] < 0.0) ? -1.0 : 1.0;
+            o.ux0 = fma(sgx * sa0, (fabs(a[0]) > 0.0) ? fmin(tau[0] * fabs(a[0]), h) : 0.0, mx0);
+            o.uy0 = fma(sgy * sa0, (fabs(a[0]) > 0.0) ? fmin(tau[1] * fabs(a[0]), h) : 0.0, my0);
+        } else status |= ISMPC_ST_FLIGHT;
+        o.x  = fma(1.0 - A0a, o.ux0, fma(A0a, x0, A0b * xd0));
+        o.xd = fma(-A0c, o.ux0, fma(A0c, x0, A0a * xd0));
+        o.y  = fma(1.0 - A0a, o.uy0, fma(A0a, y0, A0b * yd0));
+        o.yd = fma(-A0c, o.uy0, fma(A0c, y0, A0a * yd0));
+    }
+    o.status = status;
+    if (u_traj_inst) {
+        const bool stage3 = run && Grp<LPI>::bcast0(lam0_l) > c.gate;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int n = n0 + r;
+            if (n < N) {
+                double vx = 0.0, vy = 0.0;
+                if (stage3) {
+                    const double sa = (a[r] < 0.0) ? -1.0 : 1.0;
+                    vx = fma(sgx * sa, (fabs(a[r]) > 0.0) ? fmin(tau[0] * fabs(a[r]), h) : 0.0, c.midx[idx + n]);
+                    vy = fma(sgy * sa, (fabs(a[r]) > 0.0) ? fmin(tau[1] * fabs(a[r]), h) : 0.0, c.midy[idx + n]);
+                }
+                u_traj_inst[n] = run ? u[r] : 0.0; u_traj_inst[N + n] = vx; u_traj_inst[2 * N + n] = vy;
+            }
+        }
+    }
+    return deferred;
+}
+
+// One launch = one tick: record in, record out (and, in the host-driven closed loop, state fed back in place)
+template <int R, int LPI, int KF, bool SW = false>
+__device__ __forceinline__ bool tick_group_body(const DevConst& c, const int gi_raw, const int batch, const int lane,
+                                                const ismpc_tick_in* __restrict__ in_ro, ismpc_tick_in* state_rw,
+                                                ismpc_tick_out* __restrict__ out, double* __restrict__ u_traj,
+                                                int rollout_frame, unsigned char* zmark, int launch_id, double2* __restrict__ lds_wave, int* zlist = nullptr)
+{
+    const bool valid = gi_raw < batch;
+    const int gi = valid ? gi_raw : batch - 1;        // tail groups recompute the last instance and store nothing
+    STAMP_DECL;
+    STAMP(0);                                         // first instructions of the wavefront
+    const ismpc_tick_in* rec = ((rollout_frame >= 0) ? state_rw : in_ro) + gi;
+    QState s;
+    s.w = load_walk(c, rec, rollout_frame);
+    s.x = rec->com_pos[0]; s.y = rec->com_pos[1]; s.z = rec->com_pos[2];
+    s.xd = rec->com_vel[0]; s.yd = rec->com_vel[1]; s.zd = rec->com_vel[2];
+    s.ps = 0;
+    if (SW) { const int ps = rec->reserved; s.ps = (ps >= 0 && ps < c.nsets) ? ps : -1; }       // an unknown set: ISMPC_ST_BAD_INDEX, state passed through
+    QOut o;
+    const bool deferred = tick_group_core<R, LPI, KF, SW>(c, lane, s, o, (u_traj && valid) ? u_traj + (size_t)gi * 3 * c.N : nullptr, lds_wave);
+    if ((lane & (LPI - 1)) == 0 && valid) {
+        if (out) store_record(out + gi, o);
+        if (deferred) {
+            if (c.zseen) *c.zseen = launch_id;
+            if (zlist) { const int slot = atomicAdd(c.zflag, 1); if (slot < batch) zlist[slot] = gi; }
+        }
+        if (rollout_frame >= 0 && !deferred) store_feedback(c, state_rw + gi, o, s.w);
+    }
+    STAMP(5);                                         // stores issued
+    return deferred && valid;
+}
+
+#ifndef ISMPC_QUAD_WAVES
+#define ISMPC_QUAD_WAVES 4
+#endif
+// Workgroups are handed to the 8 XCDs round-robin (workgroup b runs on XCD b mod 8, each with its own L2).  The virtual block of
+// workgroup b: XCD x takes the contiguous range [x q + min(x, r), ...) of the nb blocks (q = nb / 8, r = nb mod 8) -- a bijection.
+__device__ __forceinline__ int sweep_vblock(int b, int nb)
+{
+    const int q = nb >> 3, r = nb & 7, x = b & 7;
+    return x * q + min(x, r) + (b >> 3);
+}
+// instance of launch slot `slot` (see DevConst::order); slots past the batch name no instance
+template <bool SW> __device__ __forceinline__ int slot_instance(const DevConst& c, int slot, int batch)
+{
+    if (SW) { if (c.order) return slot < batch ? c.order[slot] : batch; }
+    return slot;
+}
+template <int R, int LPI, bool SW = false>
+__global__ __launch_bounds__(64 * ISMPC_QUAD_WAVES)
+void ismpc_tick_quad(const DevConst c, const ismpc_tick_in* __restrict__ in_ro, ismpc_tick_in* state_rw,
+                     ismpc_tick_out* __restrict__ out, double* __restrict__ u_traj, int batch, int rollout_frame,
+                     unsigned char* zmark, int launch_id)
+{
+    constexpr int IPW = 64 / LPI;                      // instances per wavefront
+    __shared__ double2 lds_mid[ISMPC_QUAD_WAVES][wave_lds_double2<R, LPI>()];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int blk = (SW && c.order) ? sweep_vblock(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int wave = blk * ISMPC_QUAD_WAVES + wv;
+    if (wave * IPW >= batch) return;
+    tick_group_body<R, LPI, ISMPC_KF_MAIN, SW>(c, slot_instance<SW>(c, wave * IPW + lane / LPI, batch), batch, lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id, lds_mid[wv],
+                                               zmark ? zlist_of(zmark, batch) : nullptr);
+}
+
+// Latency variant for small batches (every wavefront resident at once): a wavefront that deferred one of its
+// instances runs the inequality fallback for it right away, with all 64 lanes, so a step is ONE launch.
+template <int R, int LPI, int RW>
+__global__ __launch_bounds__(64 * ISMPC_QUAD_WAVES, 2)      // two wavefronts per SIMD (that is all a batch that takes this kernel has)
+void ismpc_tick_quad_inline(const DevConst c, const ismpc_tick_in* __restrict__ in_ro, ismpc_tick_in* state_rw,
+                            ismpc_tick_out* __restrict__ out, double* __restrict__ u_traj, int batch, int rollout_frame,
+                            unsigned char* zmark, int launch_id, const DevConst* __restrict__ cdev)
+{
+    constexpr int IPW = 64 / LPI;
+    __shared__ double2 lds_mid[ISMPC_QUAD_WAVES][wave_lds_double2_fb<R, LPI>()];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = blockIdx.x * ISMPC_QUAD_WAVES + wv;
+    if (wave * IPW >= batch) return;
+    const bool def = tick_group_body<R, LPI, ISMPC_KF_INLINE>(c, wave * IPW + lane / LPI, batch, lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id, lds_mid[wv]);
+    unsigned long long m = __builtin_amdgcn_ballot_w64(def);
+    if (m == 0ull) return;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    for (int q = 0; q < IPW; ++q)
+        if ((m >> (LPI * q)) & 1ull)
+            fallback_call<RW>(cdev, wave * IPW + q, lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id, reinterpret_cast<double*>(lds_mid[wv]));   // (the constants in memory:
+                                                                                     // taking the address of the by-value argument would move the hot path's copy to the stack)
+}
+
+// The one-launch form for batches that do NOT fit the chip at once: the tick keeps the three wavefronts per SIMD of ismpc_tick_quad
+// (the kernel asks for them, and the compiler hands that register budget down to the fallback it calls: the fallback spills to
+// scratch instead, and only a wavefront that defers an instance runs it).  No second, normally idle, launch per step: +1-2 % at
+// 65 536 instances, +4 % at 32 768, +8 % at 16 384 (same box, scripts/ab_env.sh ISMPC_ONE_LAUNCH=0).  SW: parameter sweeps, the
+// fallback runs on the deferred instance's own set.
+// wavefronts per SIMD of ismpc_tick_quad<R, LPI, SW> (profiles/r03/kernel_resources.md): what the one-launch form asks for
+#ifndef ISMPC_OCC_R13
+#define ISMPC_OCC_R13 2
+#endif
+template <int R, bool SW> constexpr int one_occ() { return R <= 4 ? (SW ? 3 : 4) : R <= 7 ? 3 : R == 8 ? (SW ? 2 : 3) : R <= 13 ? ISMPC_OCC_R13 : 1; }
+template <int R, int LPI, int RW, bool SW>
+__global__ __launch_bounds__(64 * ISMPC_QUAD_WAVES, (one_occ<R, SW>()))
+void ismpc_tick_quad_one(const DevConst c, const ismpc_tick_in* __restrict__ in_ro, ismpc_tick_in* state_rw,
+                         ismpc_tick_out* __restrict__ out, double* __restrict__ u_traj, int batch, int rollout_frame,
+                         unsigned char* zmark, int launch_id, const DevConst* __restrict__ cdev)
+{
+    constexpr int IPW = 64 / LPI;
+    __shared__ double2 lds_mid[ISMPC_QUAD_WAVES][wave_lds_double2_fb<R, LPI>()];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int blk = (SW && c.order) ? sweep_vblock(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int wave = blk * ISMPC_QUAD_WAVES + wv;
+    if (wave * IPW >= batch) return;
+    const bool def = tick_group_body<R, LPI, ISMPC_KF_MAIN, SW>(c, slot_instance<SW>(c, wave * IPW + lane / LPI, batch), batch, lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id, lds_mid[wv]);
+    unsigned long long m = __builtin_amdgcn_ballot_w64(def);
+    if (m == 0ull) return;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    for (int q = 0; q < IPW; ++q)
+        if ((m >> (LPI * q)) & 1ull) {
+            const int gi = __builtin_amdgcn_readfirstlane(slot_instance<SW>(c, wave * IPW + q, batch));
+            const DevConst* cp = cdev;
+            if (SW) cp = c.sets + __builtin_amdgcn_readfirstlane((((rollout_frame >= 0) ? state_rw : in_ro) + gi)->reserved);   // (a deferred instance has a valid set)
+            fallback_call_one<RW, one_occ<R, SW>()>(cp, gi, lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id, reinterpret_cast<double*>(lds_mid[wv]));
+        }
+}
+
+// Closed loop inside ONE launch (Controller.cpp:297-310 bookkeeping, :346-348 feedback, :503-504 counters): instances are
+// independent, so a wavefront keeps the state of its instances in registers for `ticks` ticks and writes one trajectory
+// record per tick; nothing but the read-only tables is re-read.  Bit-identical to `ticks` launches of the per-tick kernels
+// (same tick_group_core, same fallback body).
+//   FB = false (the rollout itself): an instance whose vertical inequality rows become active at tick t parks its pre-tick
+//     state in `state`, records t in stop_tick and sits out the rest of the launch;
+//   FB = true (second launch, exits at once unless the first one parked something): one wavefront per parked instance
+//     resumes it at its tick, running the active-set fallback (all 64 lanes, through memory) at the ticks that need it.
+// Keeping the fallback out of the first kernel keeps its register budget that of the tick itself.
+template <int R, int LPI, int RW, bool FB, bool SW = false>
+__global__ __launch_bounds__(64 * ISMPC_QUAD_WAVES, 2)
+void ismpc_rollout_quad(const DevConst c, ismpc_tick_in* state, ismpc_tick_out* __restrict__ traj, int batch, int first_frame, int ticks,
+                        int* __restrict__ stop_tick, int launch_id)
+{
+    constexpr int IPW = 64 / LPI;
+    __shared__ double2 lds_mid[ISMPC_QUAD_WAVES][FB ? wave_lds_double2_fb<R, LPI>() : wave_lds_double2<R, LPI>()];
+    const int lane = threadIdx.x & 63, li = lane & (LPI - 1);
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = blockIdx.x * ISMPC_QUAD_WAVES + wv;
+    if constexpr (FB) { if (*(volatile int*)(c.zflag + 2) == 0) return; }      // nothing parked (workgroup-uniform: the first launch is done)
+    const int nwork = FB ? batch : (batch + IPW - 1) / IPW;          // FB: one instance per wavefront (every group computes it, group 0 stores)
+    for (int work = wave; work < nwork; work += FB ? (int)gridDim.x * ISMPC_QUAD_WAVES : nwork) {
+        const int gi_raw = FB ? work : work * IPW + lane / LPI;
+        const bool valid = FB ? (lane < LPI) : (gi_raw < batch);
+        const int gi = (gi_raw < batch) ? gi_raw : batch - 1;
+        int t0 = 0;
+        if constexpr (FB) { t0 = stop_tick[gi]; if (t0 < 0) continue; }
+        ismpc_tick_in* rec = state + gi;
+        QState s;
+        s.w.sim = rec->simulation_time; s.w.mpc = rec->mpc_iter; s.w.ctl = rec->control_iter; s.w.fc = rec->footstep_counter;
+        s.x = rec->com_pos[0]; s.y = rec->com_pos[1]; s.z = rec->com_pos[2];
+        s.xd = rec->com_vel[0]; s.yd = rec->com_vel[1]; s.zd = rec->com_vel[2]; s.ps = 0;
+        if (SW) { const int ps = rec->reserved; s.ps = (ps >= 0 && ps < c.nsets) ? ps : -1; }     // sweep handles: the instance's parameter set
+        bool alive = true;                                              // FB = false: false once the instance is parked
+        int stopped = -1;
+        for (int t = t0; t < ticks; ++t) {
+            const int frame = first_frame + t;
+            // caller bookkeeping in front of solve(): Controller.cpp:297-304 (enabled) and :310 -- load_walk's rollout branch
+            const Walk before = s.w;
+            if (s.w.fc >= 0 && s.w.fc < c.rows && s.w.sim >= c.ftsp_t[s.w.fc] - 1) { s.w.ctl = 0; s.w.mpc = 0; s.w.fc = s.w.fc + 1; }
+            s.w.sim = (double)frame;
+            QOut o;
+            const bool def = tick_group_core<R, LPI, ISMPC_KF_ROLLOUT, SW>(c, lane, s, o, nullptr, lds_mid[wv]);
+            const bool park = def && alive;
+            if (li == 0 && valid && alive && !def && traj) store_record(traj + (size_t)t * batch + gi, o);
+            // a deferred instance: its pre-tick state goes to memory (FB = false: to stay there; FB = true: for the fallback body)
+            if (park && valid && li == 0) {
+                rec->com_pos[0] = s.x; rec->com_pos[1] = s.y; rec->com_pos[2] = s.z;
+                rec->com_vel[0] = s.xd; rec->com_vel[1] = s.yd; rec->com_vel[2] = s.zd;
+                rec->simulation_time = before.sim; rec->mpc_iter = before.mpc; rec->control_iter = before.ctl; rec->footstep_counter = before.fc;
+            }
+            if constexpr (!FB) {
+                if (park) { alive = false; stopped = t; }
+            }
+            // feedback (Controller.cpp:346-348) and counters (:503-504), in registers; lane 0 of the group holds the result
+            s.x = Grp<LPI>::bcast0(o.x); s.y = Grp<LPI>::bcast0(o.y); s.z = Grp<LPI>::bcast0(o.z);
+            s.xd = Grp<LPI>::bcast0(o.xd); s.yd = Grp<LPI>::bcast0(o.yd); s.zd = Grp<LPI>::bcast0(o.zd);
+            s.w.ctl = s.w.ctl + 1;
+            s.w.mpc = (int)floor(s.w.ctl * c.cdt / c.dt);
+            if constexpr (FB) {
+                if (__builtin_amdgcn_ballot_w64(def && valid) != 0ull) {
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                    // (FB: one instance per wavefront, its set is wave-uniform and valid -- an invalid one never defers)
+                    tick_affine_body<RW, true>(SW ? c.sets[__builtin_amdgcn_readfirstlane(max(s.ps, 0))] : c, gi, lane, nullptr, state,
+                                               traj ? traj + (size_t)t * batch : nullptr, nullptr, frame, nullptr, 0, nullptr, 0, reinterpret_cast<double*>(lds_mid[wv]));
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                    const volatile ismpc_tick_in* vr = rec;
+                    s.x = vr->com_pos[0]; s.y = vr->com_pos[1]; s.z = vr->com_pos[2];
+                    s.xd = vr->com_vel[0]; s.yd = vr->com_vel[1]; s.zd = vr->com_vel[2];
+                    s.w.sim = vr->simulation_time; s.w.mpc = vr->mpc_iter; s.w.ctl = vr->control_iter; s.w.fc = vr->footstep_counter;
+                }
+            }
+        }
+        if (li == 0 && valid) {
+            if (alive) {
+                rec->com_pos[0] = s.x; rec->com_pos[1] = s.y; rec->com_pos[2] = s.z;
+                rec->com_vel[0] = s.xd; rec->com_vel[1] = s.yd; rec->com_vel[2] = s.zd;
+                rec->simulation_time = s.w.sim; rec->mpc_iter = s.w.mpc; rec->control_iter = s.w.ctl; rec->footstep_counter = s.w.fc;
+            }
+            if constexpr (!FB) {
+                stop_tick[gi] = stopped;
+                if (stopped >= 0) atomicAdd(c.zflag + 2, 1);
+            }
+        }
+    }
+    if constexpr (FB) {      // the last resume workgroup zeroes the parked count for the next rollout (see DevConst::zflag)
+        __syncthreads();
+        if (threadIdx.x == 0 && atomicAdd(c.zflag + 3, 1) == (int)gridDim.x - 1) { c.zflag[2] = 0; c.zflag[3] = 0; __threadfence(); }
+    }
+}
+
+// ---- ismpc_sweep_bind: counting sort of the instances of a batch by parameter set (bucket nsets: records that name no set) ----------
+__global__ __launch_bounds__(256) void sweep_sort_hist(const ismpc_tick_in* __restrict__ in, int batch, int nsets, int* __restrict__ counts)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= batch) return;
+    const int ps = in[i].reserved;
+    atomicAdd(counts + ((ps >= 0 && ps < nsets) ? ps : nsets), 1);
+}
+// exclusive scan of counts[0 .. n) in place (one workgroup; n <= 65 536 + 1): counts[k] becomes the first slot of bucket k
+__global__ __launch_bounds__(256) void sweep_sort_scan(int* __restrict__ counts, int n)
+{
+    __shared__ int part[256];
+    const int tid = threadIdx.x, per = (n + 255) / 256, lo = tid * per, hi = min(lo + per, n);
+    int s = 0;
+    for (int k = lo; k < hi; ++k) s += counts[k];
+    part[tid] = s;
+    __syncthreads();
+    if (tid == 0) { int run = 0; for (int k = 0; k < 256; ++k) { const int v = part[k]; part[k] = run; run += v; } }
+    __syncthreads();
+    int run = part[tid];
+    for (int k = lo; k < hi; ++k) { const int v = counts[k]; counts[k] = run; run += v; }
+}
+__global__ __launch_bounds__(256) void sweep_sort_scatter(const ismpc_tick_in* __restrict__ in, int batch, int nsets, int* __restrict__ cursor, int* __restrict__ order)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= batch) return;
+    const int ps = in[i].reserved;
+    order[atomicAdd(cursor + ((ps >= 0 && ps < nsets) ? ps : nsets), 1)] = i;      // (the order INSIDE a bucket is whatever the atomics give: no result depends on it)
+}
+
+}  // namespace

@@ -22,13 +22,13 @@
 #include <vector>
 
 #include "ismpc_group.h"
+#include "ismpc_host.hpp"
 
 namespace {
 
 thread_local std::string g_gerr = "";
 int gfail(int code, const std::string& msg) { g_gerr = msg; return code; }
-#define G_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
-    return gfail(ISMPC_E_NO_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+#define G_HIP(expr) ISMPC_HIP_TRY(gfail, expr)
 
 // ---- RCCL, bound at run time ----------------------------------------------------------------------------------------
 // A process that already maps a copy of RCCL (a torch process maps torch/lib/librccl.so, which has no SONAME) must not get a
