@@ -503,10 +503,8 @@ int ismpc_sweep_bind(ismpc_handle* h, int batch, const ismpc_tick_in* in_dev, vo
     const int nb = h->c.nsets + 1;
     if (batch + nb > h->order_cap) {
         HIP_TRY(hipDeviceSynchronize());                       // (a set-up call: launches that still read the old order finish first)
-        if (h->order) HIP_TRY(hipFree(h->order));
-        h->order = nullptr; h->order_cap = 0; h->order_batch = 0;
-        HIP_TRY(hipMalloc((void**)&h->order, sizeof(int) * (size_t)(batch + nb)));
-        h->order_cap = batch + nb;
+        h->order_batch = 0;
+        ISMPC_GROW_SYNC(fail, h->order, h->order_cap, batch + nb, sizeof(int) * (size_t)(batch + nb));
     }
     int* cursor = h->order + batch;
     HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(int) * (size_t)nb, s));
@@ -758,18 +756,8 @@ int ismpc_reserve(ismpc_handle* h, int max_batch)
 {
     if (!h || max_batch < 0) return fail(ISMPC_E_INVALID, "bad argument");
     ON_DEVICE(h);
-    if (h->z_fallback && max_batch > h->zmark_cap) {
-        if (h->zmark) HIP_TRY(hipFree(h->zmark));
-        h->zmark = nullptr; h->zmark_cap = 0;
-        HIP_TRY(hipMalloc((void**)&h->zmark, zscratch_bytes(max_batch)));
-        h->zmark_cap = max_batch;
-    }
-    if (max_batch > h->zstop_cap) {
-        if (h->zstop) HIP_TRY(hipFree(h->zstop));
-        h->zstop = nullptr; h->zstop_cap = 0;
-        HIP_TRY(hipMalloc((void**)&h->zstop, sizeof(int) * (size_t)max_batch));
-        h->zstop_cap = max_batch;
-    }
+    if (h->z_fallback && max_batch > h->zmark_cap) ISMPC_GROW_SYNC(fail, h->zmark, h->zmark_cap, max_batch, zscratch_bytes(max_batch));
+    if (max_batch > h->zstop_cap) ISMPC_GROW_SYNC(fail, h->zstop, h->zstop_cap, max_batch, sizeof(int) * (size_t)max_batch);
     return ISMPC_OK;
 }
 

@@ -1,5 +1,5 @@
 // Host plumbing shared by the three C ABIs (ismpc_hip.hip, ismpc_a_hip.hip, ismpc_group.hip): the device guard, the early return on a
-// HIP error, and stream-ordered growth of scratch that outlives a call.  Each ABI keeps its own thread-local error string and
+// HIP error, and growth (stream-ordered or synchronous) of scratch that outlives a call.  Each ABI keeps its own thread-local error string and
 // its own `int fail(code, message)`; the macros below take that function by name.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -48,4 +48,10 @@ template <class H> struct StreamMark { H* h; hipStream_t s; ~StreamMark() { h->l
     if (p_) ISMPC_HIP_TRY(fail_, hipFreeAsync(p_, s_)); \
     p_ = nullptr; cap_ = 0; \
     ISMPC_HIP_TRY(fail_, hipMallocAsync((void**)&p_, bytes_, s_)); \
+    cap_ = new_cap_; } while (0)
+// The synchronous twin, for set-up calls (the ABI's reserve): same order, same reason to be a macro ("hipFree(h->prev): ...").
+#define ISMPC_GROW_SYNC(fail_, p_, cap_, new_cap_, bytes_) do { \
+    if (p_) ISMPC_HIP_TRY(fail_, hipFree(p_)); \
+    p_ = nullptr; cap_ = 0; \
+    ISMPC_HIP_TRY(fail_, hipMalloc((void**)&p_, bytes_)); \
     cap_ = new_cap_; } while (0)

@@ -232,6 +232,30 @@ def test_foot_files_from_device_rollout(FA, name, tmp_path):
 def test_other_horizons_against_oracle(FA, kind_name, over, backend):
     """F_A = ceil(C/step)+1 footsteps for long horizons (SURVEY.md 'Index limits'); every (rows-per-lane, F) kernel
     instantiation that the BASELINE configs reach, nominal closed loop + pushed single ticks, against the oracle."""
+    _closed_loop_and_pushes_against_oracle(FA, kind_name, over, backend)
+
+
+# The workgroup-per-QP kernel (csrc/ismpc_a_block.hpp): what a handle runs when F is outside the wave kernels' 3..6, or when it was
+# created under ISMPC_A_KERNEL=block.  Nothing in the output records names the kernel that ran: the first two cases reach this one because
+# launch_f (csrc/ismpc_a_wave.hpp) has no instantiation outside F = 3..6 -- whoever adds one moves these cases to an F it still lacks.
+WORKGROUP_CASES = [("trot", dict(C=240, P=480, F=7, step=40, ds=24), None),      # F > 6; working set <= 248 of QCAP = 264, C + F = 247 <= 256
+                   ("walk", dict(C=40, P=80, F=2), None),                        # F < 3
+                   ("walk", dict(C=100, P=200, F=3), "block")]                   # a wave-kernel shape, sent to the workgroup kernel by the knob
+
+
+@pytest.mark.parametrize("kind_name,over,knob", WORKGROUP_CASES)
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_workgroup_kernel_against_oracle(FA, kind_name, over, knob, backend, monkeypatch):
+    """The same closed loop + pushed ticks, same tolerances, on the shapes that reach ismpc_a_tick_kernel."""
+    if knob:
+        monkeypatch.setenv("ISMPC_A_KERNEL", knob)                               # read by ismpc_a_create
+    else:
+        monkeypatch.delenv("ISMPC_A_KERNEL", raising=False)
+    _closed_loop_and_pushes_against_oracle(FA, kind_name, over, backend)
+
+
+def _closed_loop_and_pushes_against_oracle(FA, kind_name, over, backend):
+    """Nominal closed loop (130 ticks for "gi", 70 for "ref"), then 12 pushed single ticks from the end state, against the oracle."""
     import torch
     from oracle import oracle_a as A
     kind = A.WALK if kind_name == "walk" else A.TROT
@@ -246,20 +270,30 @@ def test_other_horizons_against_oracle(FA, kind_name, over, backend):
     st = q_to_dev(gen.initial_state(g.disp_C, batch=1))
     out = q_from_dev(gen.rollout_torch(st, ticks), FA.OUT_A)[:, 0]
     torch.cuda.synchronize()
-    ref = sim.run(ticks)
-    assert (out["status"] == 0).all() and (ref["rv"] == 0).all()
-    assert np.abs(out["com_before"] - ref["com_before"]).max() <= 1e-6 * max(1.0, np.abs(ref["com_before"]).max())
-    assert np.abs(out["u0"] - ref["u0"]).max() <= TOL_U0[backend] and np.abs(out["f0"] - ref["f0"]).max() <= 1e-7
     # pushed ticks from the end state
     rng = np.random.default_rng(1)
     fin = q_from_dev(st, FA.STATE_A)
     pushes = np.stack([rng.uniform(-0.03, 0.03, 12), rng.uniform(-0.05, 0.05, 12)], 1)
     d_st = q_to_dev(np.repeat(fin, 12)); d_push = torch.from_numpy(pushes.copy()).to("cuda:0")
     o2 = q_from_dev(gen.tick_torch(d_st, d_push), FA.OUT_A)
+    ref = sim.run(ticks)
     base = sim.state.copy(); plan = sim.get_plan()
+    rs = []
     for i in range(12):
         sim.state = base; sim.set_plan(*plan)
-        r = sim.tick(tuple(pushes[i]))
+        rs.append(sim.tick(tuple(pushes[i])))
+    # every figure first (pytest -s), then the assertions
+    _record_maxima(f"closed_loop_and_pushes:{kind_name}:C{over['C']}:F{over['F']}:{os.environ.get('ISMPC_A_KERNEL', 'default')}:{backend}", dict(
+        status_nonzero=int((out["status"] != 0).sum()), ref_rv_nonzero=int((ref["rv"] != 0).sum()),
+        com_rel=np.abs(out["com_before"] - ref["com_before"]).max() / max(1.0, np.abs(ref["com_before"]).max()),
+        u0=np.abs(out["u0"] - ref["u0"]).max(), f0=np.abs(out["f0"] - ref["f0"]).max(),
+        push_status_nonzero=int((o2["status"] != 0).sum()), push_rv_nonzero=int(sum(int(r["rv"][0] != 0 or r["rv"][1] != 0) for r in rs)),
+        push_u0_rel=max(np.abs(o2["u0"][i] - r["u0"]).max() / max(1.0, np.abs(r["u0"]).max()) for i, r in enumerate(rs)),
+        push_f0=max(np.abs(o2["f0"][i] - r["f0"]).max() for i, r in enumerate(rs))))
+    assert (out["status"] == 0).all() and (ref["rv"] == 0).all()
+    assert np.abs(out["com_before"] - ref["com_before"]).max() <= 1e-6 * max(1.0, np.abs(ref["com_before"]).max())
+    assert np.abs(out["u0"] - ref["u0"]).max() <= TOL_U0[backend] and np.abs(out["f0"] - ref["f0"]).max() <= 1e-7
+    for i, r in enumerate(rs):
         assert r["rv"][0] == 0 and r["rv"][1] == 0
         assert np.abs(o2["u0"][i] - r["u0"]).max() <= TOL_U0[backend] * max(1.0, np.abs(r["u0"]).max()), (i, o2["u0"][i], r["u0"])
         assert np.abs(o2["f0"][i] - r["f0"]).max() <= 1e-7
