@@ -220,6 +220,20 @@ int         ismpc_get_midpoint(const ismpc_handle* h, double* dst, int capacity_
  * deferred list, fallback workgroups done, instances parked by an in-kernel rollout, resume workgroups done.  All four
  * are 0 between calls, whatever was launched before (ticks, rollouts, hipGraph replays of a captured step).          */
 int         ismpc_fallback_counters(ismpc_handle* h, int* out4);
+/* Which kernel the handle's most recent step (ismpc_solve_batch*) or closed loop (ismpc_rollout_device) enqueued, as the host
+ * recorded it where it launched (no device work, no synchronisation): out8 = { kernel family (ISMPC_KERNEL_*), lanes per
+ * instance, R = horizon samples per lane, RW = samples per lane of the inequality fallback's one-instance-per-wavefront body,
+ * 1 for the parameter-sweep instantiation, kernels enqueued per step (2 = tick + fallback launch, rollout + resume launch),
+ * batch, 1 when the ismpc_sweep_bind order placed the instances }.  All zero before the first launch; a closed loop run as
+ * one launch per tick (ISMPC_ROLLOUT=host, N > 128) reports its last tick.                                              */
+#define ISMPC_KERNEL_NONE         0
+#define ISMPC_KERNEL_QUAD         1   /* ismpc_tick_quad, followed by ismpc_tick_affine_fallback (the two-launch form)   */
+#define ISMPC_KERNEL_QUAD_INLINE  2   /* ismpc_tick_quad_inline: every wavefront resident at once                        */
+#define ISMPC_KERNEL_QUAD_ONE     3   /* ismpc_tick_quad_one: one launch beyond the resident size                        */
+#define ISMPC_KERNEL_ROLLOUT_QUAD 4   /* ismpc_rollout_quad and its resume launch                                        */
+#define ISMPC_KERNEL_AFFINE       5   /* ismpc_tick_affine: one instance per wavefront (ISMPC_PATH=wave, 128 < N <= 256)   */
+#define ISMPC_KERNEL_DENSE        6   /* ismpc_tick_dense (ISMPC_PATH=dense)                                             */
+int         ismpc_last_launch_info(const ismpc_handle* h, int* out8);
 int         ismpc_set_timing(ismpc_handle* h, int enabled);
 double      ismpc_last_kernel_ms(ismpc_handle* h);
 

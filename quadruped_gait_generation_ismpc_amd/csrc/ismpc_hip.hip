@@ -93,6 +93,7 @@ struct ismpc_handle {
     bool sweep = false;           // ismpc_create_sweep: K parameter sets, tables built on the device (csrc/ismpc_sweep.hip)
     ismpc::SweepSlabs sw; std::vector<ismpc_params> sets; std::vector<double> ftsp;   // (the plan as given: ismpc_sweep_verify_tables rebuilds a set on the host)
     int* order = nullptr; int order_cap = 0, order_batch = 0;   // ismpc_sweep_bind: instances of the bound batch sorted by parameter set (+ nsets + 1 bucket cursors)
+    int last_launch[8] = {0, 0, 0, 0, 0, 0, 0, 0};             // ismpc_last_launch_info: what the most recent step or rollout enqueued (plain host stores)
     hipStream_t last_stream = nullptr; bool used = false;   // stream of the previous launch: zmark / zstop outlive a call and are re-allocated
                                                             // only after that stream has drained (grow_sync)
 };
@@ -182,6 +183,11 @@ int launch(ismpc_handle* h, int batch, const ismpc_tick_in* in, ismpc_tick_in* s
     auto tick = [&](auto kernel, dim3 g, dim3 b, size_t lds, const DevConst& c, auto... more) {
         hipLaunchKernelGGL(kernel, g, b, lds, s, c, in, state, out, u_traj, batch, rollout_frame, more...);
     };
+    // what this step enqueues, for ismpc_last_launch_info: written where the kernel is launched, from the same shape values
+    auto note = [&](int family, int lanes, int r, int rw, bool sw, int kernels, bool ordered) {
+        const int v[8] = {family, lanes, r, rw, sw ? 1 : 0, kernels, batch, ordered ? 1 : 0};
+        std::memcpy(h->last_launch, v, sizeof(v));
+    };
     if (!h->dense_path) {
         // fast path: wavefront per instance, 4 per workgroup; then the (normally empty) inequality fallback
         const dim3 grid((batch + 3) / 4), block(256);
@@ -219,13 +225,19 @@ int launch(ismpc_handle* h, int batch, const ismpc_tick_in* in, ismpc_tick_in* s
                 if (lpi != 16 && lpi != 8) return fail(ISMPC_E_UNSUPPORTED, "parameter sweep: 16 or 8 lanes per instance");
                 if (one_big) {
                     quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
-                        if constexpr (LL != 32) tick(ismpc_tick_quad_one<RR, LL, RW_, true>, qgrid, qblock, 0, cq, zm, lid, cdev);
+                        if constexpr (LL != 32) {
+                            tick(ismpc_tick_quad_one<RR, LL, RW_, true>, qgrid, qblock, 0, cq, zm, lid, cdev);
+                            note(ISMPC_KERNEL_QUAD_ONE, LL, RR, RW_, true, 1, cq.order != nullptr);
+                        }
                     });
                     HIP_TRY(hipGetLastError());
                     return ISMPC_OK;
                 }
-                quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto) {
-                    if constexpr (LL != 32) tick(ismpc_tick_quad<RR, LL, true>, qgrid, qblock, 0, cq, zm, lid);
+                quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
+                    if constexpr (LL != 32) {
+                        tick(ismpc_tick_quad<RR, LL, true>, qgrid, qblock, 0, cq, zm, lid);
+                        note(ISMPC_KERNEL_QUAD, LL, RR, RW_, true, zm ? 2 : 1, cq.order != nullptr);
+                    }
                 });
                 if (zm) {
                     if (R == 1) tick(ismpc_tick_affine_fallback<1, true>, fgrid, block, 0, h->c, zm, lid);
@@ -236,16 +248,25 @@ int launch(ismpc_handle* h, int batch, const ismpc_tick_in* in, ismpc_tick_in* s
             }
             // every wavefront resident at once (<= 2 per SIMD) and a fallback to run: one launch that handles deferred instances itself
             if (zm && h->one_launch >= 1 && h->cus > 0 && waves <= 8 * h->cus) {
-                quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) { tick(ismpc_tick_quad_inline<RR, LL, RW_>, qgrid, qblock, 0, cq, zm, lid, cdev); });
+                quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
+                    tick(ismpc_tick_quad_inline<RR, LL, RW_>, qgrid, qblock, 0, cq, zm, lid, cdev);
+                    note(ISMPC_KERNEL_QUAD_INLINE, LL, RR, RW_, false, 1, false);
+                });
                 HIP_TRY(hipGetLastError());
                 return ISMPC_OK;
             }
             if (one_big) {                  // any other batch size: one launch too, at the tick's own three wavefronts per SIMD
-                quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) { tick(ismpc_tick_quad_one<RR, LL, RW_, false>, qgrid, qblock, 0, cq, zm, lid, cdev); });
+                quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
+                    tick(ismpc_tick_quad_one<RR, LL, RW_, false>, qgrid, qblock, 0, cq, zm, lid, cdev);
+                    note(ISMPC_KERNEL_QUAD_ONE, LL, RR, RW_, false, 1, false);
+                });
                 HIP_TRY(hipGetLastError());
                 return ISMPC_OK;
             }
-            quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto) { tick(ismpc_tick_quad<RR, LL>, qgrid, qblock, 0, cq, zm, lid); });
+            quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
+                tick(ismpc_tick_quad<RR, LL>, qgrid, qblock, 0, cq, zm, lid);
+                note(ISMPC_KERNEL_QUAD, LL, RR, RW_, false, zm ? 2 : 1, false);
+            });
             if (zm) {
                 if (R == 1) tick(ismpc_tick_affine_fallback<1>, fgrid, block, 0, h->c, zm, lid);
                 else        tick(ismpc_tick_affine_fallback<2>, fgrid, block, 0, h->c, zm, lid);
@@ -262,6 +283,7 @@ int launch(ismpc_handle* h, int batch, const ismpc_tick_in* in, ismpc_tick_in* s
                 tick(ismpc_tick_affine<RR>, agrid, ablock, 0, h->c, zm, lid);
                 if (zm) tick(ismpc_tick_affine_fallback<RR>, fgrid, block, 0, h->c, zm, lid);
             }
+            note(ISMPC_KERNEL_AFFINE, 64, RR, RR, h->sweep, zm ? 2 : 1, false);
         };
         if (!wave_shape(R, affine)) return fail(ISMPC_E_UNSUPPORTED, "horizon N > 256");
         HIP_TRY(hipGetLastError());
@@ -275,6 +297,7 @@ int launch(ismpc_handle* h, int batch, const ismpc_tick_in* in, ismpc_tick_in* s
         if (waves == 16)     tick(ismpc_tick_dense<RR, 16>, grid, dim3(64 * 16), lds, h->c);
         else if (waves == 8) tick(ismpc_tick_dense<RR, 8>, grid, dim3(64 * 8), lds, h->c);
         else                 tick(ismpc_tick_dense<RR, 4>, grid, dim3(64 * 4), lds, h->c);
+        note(ISMPC_KERNEL_DENSE, 64, RR, 0, false, 1, false);
     };
     if (!wave_shape(R, dense)) return fail(ISMPC_E_UNSUPPORTED, "horizon N > 256");
     HIP_TRY(hipGetLastError());
@@ -704,14 +727,24 @@ int ismpc_rollout_device(ismpc_handle* h, int batch, ismpc_tick_in* state_dev, i
             hipLaunchKernelGGL(first, qgrid, qblock, 0, s, cq, state_dev, traj_dev, batch, first_frame, ticks, h->zstop, lid);
             hipLaunchKernelGGL(resume, rgrid, qblock, 0, s, cq, state_dev, traj_dev, batch, first_frame, ticks, h->zstop, lid);
         };
+        auto note = [&](int lanes, int r, int rw) {          // (ismpc_last_launch_info: the rollout and its resume launch)
+            const int v[8] = {ISMPC_KERNEL_ROLLOUT_QUAD, lanes, r, rw, h->sweep ? 1 : 0, 2, batch, 0};
+            std::memcpy(h->last_launch, v, sizeof(v));
+        };
         // (a sweep handle rolls out at 16 lanes per instance: the SW kernels are instantiated for that shape only)
         if (h->sweep && lpi != 16) return fail(ISMPC_E_UNSUPPORTED, "parameter sweep: rollouts take 16 lanes per instance");
         if (h->sweep)
             quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
-                if constexpr (LL == 16) roll(ismpc_rollout_quad<RR, 16, RW_, false, true>, ismpc_rollout_quad<RR, 16, RW_, true, true>);
+                if constexpr (LL == 16) {
+                    roll(ismpc_rollout_quad<RR, 16, RW_, false, true>, ismpc_rollout_quad<RR, 16, RW_, true, true>);
+                    note(16, RR, RW_);
+                }
             });
         else
-            quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) { roll(ismpc_rollout_quad<RR, LL, RW_, false>, ismpc_rollout_quad<RR, LL, RW_, true>); });
+            quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
+                roll(ismpc_rollout_quad<RR, LL, RW_, false>, ismpc_rollout_quad<RR, LL, RW_, true>);
+                note(LL, RR, RW_);
+            });
         HIP_TRY(hipGetLastError());
     } else {
         for (int t = 0; t < ticks; ++t) {
@@ -769,6 +802,13 @@ int ismpc_debug_stamps(unsigned long long* dst, int reset)
     return 0;
 }
 #endif
+
+int ismpc_last_launch_info(const ismpc_handle* h, int* out8)
+{
+    if (!h || !out8) return fail(ISMPC_E_INVALID, "null argument");
+    std::memcpy(out8, h->last_launch, sizeof(h->last_launch));
+    return ISMPC_OK;
+}
 
 int ismpc_fallback_counters(ismpc_handle* h, int* out4)
 {

@@ -18,6 +18,8 @@ from ._lib import Params, TICK_IN, TICK_OUT
 ST_X_INFEASIBLE, ST_Y_INFEASIBLE, ST_Z_INEQ_ACTIVE, ST_BAD_INDEX = 1, 2, 4, 8
 ST_FLIGHT, ST_TICK_SKIPPED, ST_Z_NAN, ST_Z_FAILED = 16, 32, 64, 128
 ST_ERROR_MASK = ST_X_INFEASIBLE | ST_Y_INFEASIBLE | ST_BAD_INDEX | ST_Z_FAILED
+# ISMPC_KERNEL_* of include/ismpc.h, by value: the kernel family ismpc_last_launch_info reports
+KERNEL_FAMILIES = ("none", "quad", "quad_inline", "quad_one", "rollout_quad", "affine", "dense")
 
 
 class IsmpcError(RuntimeError):
@@ -199,6 +201,15 @@ class MPCSolver:
         a = np.zeros(4, dtype=np.int32)
         self._check(self._lib.ismpc_fallback_counters(self._h, a.ctypes.data_as(C.c_void_p)))
         return tuple(int(v) for v in a)
+
+    def launch_info(self):
+        """ismpc_last_launch_info: which kernel the most recent step or rollout of this handle enqueued, as recorded by the host at the
+        launch.  family is one of KERNEL_FAMILIES; lanes, R, RW are the instantiated shape; kernels is 1 or 2 launches per step."""
+        a = np.zeros(8, dtype=np.int32)
+        self._check(self._lib.ismpc_last_launch_info(self._h, a.ctypes.data_as(C.c_void_p)))
+        v = [int(x) for x in a]
+        return {"family": KERNEL_FAMILIES[v[0]], "lanes": v[1], "R": v[2], "RW": v[3], "sweep": bool(v[4]), "kernels": v[5],
+                "batch": v[6], "bound_order": bool(v[7])}
 
     def set_timing(self, enabled=True):
         self._check(self._lib.ismpc_set_timing(self._h, 1 if enabled else 0))

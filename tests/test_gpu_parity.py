@@ -36,32 +36,37 @@ _solvers = {}
 # instance per wavefront; per-tick MFMA formulation
 PATHS = ("affine", "lpi8", "lpi32", "auto", "wave", "dense")
 _ENV = {"affine": {"ISMPC_PATH": "affine", "ISMPC_LPI": "16"}, "lpi8": {"ISMPC_PATH": "affine", "ISMPC_LPI": "8"},
-        "lpi32": {"ISMPC_PATH": "affine", "ISMPC_LPI": "32"}, "auto": {"ISMPC_PATH": "affine"},       # auto: 32 up to 2 048 instances, 16 above
+        "lpi32": {"ISMPC_PATH": "affine", "ISMPC_LPI": "32"}, "auto": {"ISMPC_PATH": "affine"},       # auto: 32 lanes up to 2 048 instances, 16 up to 8 192, 8 beyond (closed loops keep 16)
         "hostloop32": {"ISMPC_PATH": "affine", "ISMPC_LPI": "32", "ISMPC_ROLLOUT": "host"},
         "wave": {"ISMPC_PATH": "wave"}, "dense": {"ISMPC_PATH": "dense"},
         "hostloop": {"ISMPC_PATH": "affine", "ISMPC_LPI": "16", "ISMPC_ROLLOUT": "host"},
         "hostloop8": {"ISMPC_PATH": "affine", "ISMPC_LPI": "8", "ISMPC_ROLLOUT": "host"}}
 
 
+def new_solver(q, N, path="affine", plan=None, **over):
+    """A handle of its own (the caller closes it): one that no earlier test has launched on."""
+    p = q.default_params(N=N, **over)
+    ftsp = q.reference_plan(params=p)
+    if plan == "stairs":
+        for i in range(1, ftsp.shape[0]):
+            ftsp[i, 2] = 0.01 * ((i // 3) % 4)
+    saved = {k: os.environ.get(k) for k in ("ISMPC_PATH", "ISMPC_LPI", "ISMPC_ROLLOUT")}
+    for k in saved:
+        os.environ.pop(k, None)
+    os.environ.update(_ENV[path])
+    try:
+        return q.MPCSolver(ftsp, params=p)
+    finally:
+        for k, v in saved.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+
+
 def solver_for(q, N, path="affine", plan=None, **over):
     key = (N, path, plan, tuple(sorted(over.items())))
     if key not in _solvers:
-        p = q.default_params(N=N, **over)
-        ftsp = q.reference_plan(params=p)
-        if plan == "stairs":
-            for i in range(1, ftsp.shape[0]):
-                ftsp[i, 2] = 0.01 * ((i // 3) % 4)
-        saved = {k: os.environ.get(k) for k in ("ISMPC_PATH", "ISMPC_LPI", "ISMPC_ROLLOUT")}
-        for k in saved:
-            os.environ.pop(k, None)
-        os.environ.update(_ENV[path])
-        try:
-            _solvers[key] = q.MPCSolver(ftsp, params=p)
-        finally:
-            for k, v in saved.items():
-                os.environ.pop(k, None)
-                if v is not None:
-                    os.environ[k] = v
+        _solvers[key] = new_solver(q, N, path, plan, **over)
     return _solvers[key]
 
 
@@ -85,13 +90,14 @@ def assert_parity(q, out, ref, ok=None, z_fallback=True):
     assert (out["status"][ok] == ref["status"][ok]).all()
 
 
-def _on_feasibility_boundary(q, N, rec, band):
+def _on_feasibility_boundary(q, N, rec, band, **over):
     """Is one of the two horizontal QPs of this instance within `band` (relative) of infeasibility?  Feasible <=>
     |beq - a'mid| <= h sum|a| (a box around mid and one equality row); evaluated from the decision trajectories of the
-    HIP path run with the ZMP box widened by (1 +- band)."""
+    HIP path run with the ZMP box widened by (1 +- band).  over: the other parameters the instance runs with."""
     res = []
+    rec = rec.copy(); rec["reserved"] = 0
     for scale in (1.0 - band, 1.0 + band):
-        s = solver_for(q, N, "affine", foot_width=0.09 * scale, first_step_halfwidth=1.0 * scale)
+        s = solver_for(q, N, "affine", **dict(over, foot_width=over.get("foot_width", 0.09) * scale, first_step_halfwidth=1.0 * scale))
         o = s.solve_batch(np.array([rec], dtype=q.TICK_IN))
         res.append(int(o["status"][0]) & (q.ST_X_INFEASIBLE | q.ST_Y_INFEASIBLE))
     return res[0] != res[1]
@@ -336,54 +342,77 @@ def test_closed_loop_rollout_on_device(q, N, ticks, path):
     assert fin["simulation_time"][0] == ticks - 1
 
 
-def test_full_size_properties(q, O):
+@pytest.mark.parametrize("path", ["affine", "auto"])
+def test_full_size_properties(q, O, path):
     """BASELINE config 2/3 sizes (1 024, the 8 192 shard and the full 65 536): properties that need no oracle, plus the oracle on a
-    random sample of each batch.
+    random sample of each batch.  affine: 16 lanes per instance at every size; auto: the kernel the default dispatch ships at each size
+    (at 65 536 the one bench.py reports), asserted through launch_info() before anything is compared.
     x/y QPs (MPCSolver.cpp:395-396): equality row satisfied, box respected, and the solution has the
     KKT form u = clip(mid - nu * a) with ONE multiplier nu; z QP: u_i = 0 on the equality samples."""
     import torch
     from quadruped_gait_generation_ismpc_amd import workload
     N = 100
-    s = solver_for(q, N)
-    mid = s.midpoint()
+    # auto: a handle of its own per size -- the launch form also follows the deferrals the handle has seen in its last 4 096 launches
+    s = solver_for(q, N) if path == "affine" else None
+    mid = solver_for(q, N).midpoint()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    one_launch = max(0, min(3, int(os.environ.get("ISMPC_ONE_LAUNCH", "2"))))      # 0: the two-launch form on every step
     for batch in (1024, 8192, 65536):
         tin = workload.make_batch(N, batch, seed=11)
         d_in = q.to_device(tin)
         traj = torch.zeros((batch, 3, N), dtype=torch.float64, device="cuda:0")
-        out = q.from_device(s.solve_batch_torch(d_in, u_traj=traj), q.TICK_OUT)
-        torch.cuda.synchronize()
-        t = traj.cpu().numpy()
-        again = q.from_device(s.solve_batch_torch(d_in), q.TICK_OUT)
-        assert again.tobytes() == out.tobytes()               # deterministic
-        st = out["status"]
-        run = ((st & (q.ST_ERROR_MASK | q.ST_FLIGHT)) == 0)
-        assert 0.6 < run.mean() < 0.9 and 0.15 < ((st & q.ST_FLIGHT) != 0).mean() < 0.3
-        idx = tin["simulation_time"].astype(int)
-        win = idx[:, None] + np.arange(N)[None, :]
-        half = np.where(tin["footstep_counter"] > 1, 0.045, 1.0)[:, None]
-        for ax in (0, 1):
-            u = t[:, 1 + ax]; m = mid[win, ax]
-            v = u - m
-            assert (np.abs(v[run]) <= half[run] + 1e-12).all()
-        # vertical equalities
-        fc = tin["footstep_counter"]; it = tin["mpc_iter"]
-        for b in np.where(((st & q.ST_ERROR_MASK) == 0) & (fc > 1))[0][:512]:
-            lo, hi = (35 - it[b], 45 - it[b]) if it[b] < 35 else (0, 45 - it[b])
-            assert np.all(t[b, 0, lo:hi] == 0.0)
-            assert np.abs(t[b, 0, hi:hi + 20]).min() > 1.0
-        # flight instances coast: x' = x + dt * xd
-        fl = (st & q.ST_FLIGHT) != 0
-        assert np.allclose(out["com_pos"][fl][:, :2], tin["com_pos"][fl][:, :2] + 0.01 * tin["com_vel"][fl][:, :2], rtol=0, atol=1e-15)
-        # the equality row of both horizontal QPs holds: a'u = beq with a, beq recomputed by the oracle for a sample, and the
-        # whole record against the oracle (reference qpOASES where oracle/_ref is built) for the same sample
-        pick = np.random.default_rng(batch).choice(batch, 192, replace=False)
-        ref, info = O.Oracle(O.default_params(N)).solve(tin[pick])
-        assert_parity(q, out[pick], ref)
-        # status equality by the rule of test_against_oracle_seeded: the only admissible difference is a horizontal QP within
-        # 1e-9 (relative) of its feasibility boundary, which qpOASES' own termination test may classify either way
-        for b in np.where(out["status"][pick] != ref["status"])[0]:
-            assert ((out["status"][pick][b] ^ ref["status"][b]) & ~(q.ST_X_INFEASIBLE | q.ST_Y_INFEASIBLE)) == 0
-            assert _on_feasibility_boundary(q, N, tin[pick[b]], band=1e-9), (batch, pick[b], out["status"][pick][b], ref["status"][b])
+        if path == "auto":
+            s = new_solver(q, N, "auto")
+        try:
+            out = q.from_device(s.solve_batch_torch(d_in, u_traj=traj), q.TICK_OUT)
+            torch.cuda.synchronize()
+            if path == "auto":
+                linfo = s.launch_info()
+                print(f"launch_info[auto-{batch}] = {linfo}")
+                lanes = 32 if batch <= 2048 else 16 if batch <= 8192 else 8
+                resident = (batch * lanes + 63) // 64 <= 8 * cus              # the residency rule of launch()
+                family, kernels = ("quad_inline", 1) if (resident and one_launch >= 1) else ("quad_one", 1) if one_launch >= 2 else ("quad", 2)
+                assert (linfo["family"], linfo["lanes"], linfo["kernels"], linfo["batch"], linfo["sweep"]) == (family, lanes, kernels, batch, False), linfo
+                assert (linfo["R"], linfo["RW"]) == {32: (4, 2), 16: (7, 2), 8: (13, 2)}[lanes], linfo
+                if batch == 1024:
+                    assert resident and (linfo["lanes"], linfo["family"]) == (32, "quad_inline" if one_launch >= 1 else "quad")
+                if batch == 65536:
+                    assert not resident and (linfo["lanes"], linfo["family"], linfo["R"]) == (8, "quad_one" if one_launch >= 2 else "quad", 13)
+            t = traj.cpu().numpy()
+            again = q.from_device(s.solve_batch_torch(d_in), q.TICK_OUT)
+            assert again.tobytes() == out.tobytes()               # deterministic
+            st = out["status"]
+            run = ((st & (q.ST_ERROR_MASK | q.ST_FLIGHT)) == 0)
+            assert 0.6 < run.mean() < 0.9 and 0.15 < ((st & q.ST_FLIGHT) != 0).mean() < 0.3
+            idx = tin["simulation_time"].astype(int)
+            win = idx[:, None] + np.arange(N)[None, :]
+            half = np.where(tin["footstep_counter"] > 1, 0.045, 1.0)[:, None]
+            for ax in (0, 1):
+                u = t[:, 1 + ax]; m = mid[win, ax]
+                v = u - m
+                assert (np.abs(v[run]) <= half[run] + 1e-12).all()
+            # vertical equalities
+            fc = tin["footstep_counter"]; it = tin["mpc_iter"]
+            for b in np.where(((st & q.ST_ERROR_MASK) == 0) & (fc > 1))[0][:512]:
+                lo, hi = (35 - it[b], 45 - it[b]) if it[b] < 35 else (0, 45 - it[b])
+                assert np.all(t[b, 0, lo:hi] == 0.0)
+                assert np.abs(t[b, 0, hi:hi + 20]).min() > 1.0
+            # flight instances coast: x' = x + dt * xd
+            fl = (st & q.ST_FLIGHT) != 0
+            assert np.allclose(out["com_pos"][fl][:, :2], tin["com_pos"][fl][:, :2] + 0.01 * tin["com_vel"][fl][:, :2], rtol=0, atol=1e-15)
+            # the equality row of both horizontal QPs holds: a'u = beq with a, beq recomputed by the oracle for a sample, and the
+            # whole record against the oracle (reference qpOASES where oracle/_ref is built) for the same sample
+            pick = np.random.default_rng(batch).choice(batch, 192, replace=False)
+            ref, info = O.Oracle(O.default_params(N)).solve(tin[pick])
+            assert_parity(q, out[pick], ref)
+            # status equality by the rule of test_against_oracle_seeded: the only admissible difference is a horizontal QP within
+            # 1e-9 (relative) of its feasibility boundary, which qpOASES' own termination test may classify either way
+            for b in np.where(out["status"][pick] != ref["status"])[0]:
+                assert ((out["status"][pick][b] ^ ref["status"][b]) & ~(q.ST_X_INFEASIBLE | q.ST_Y_INFEASIBLE)) == 0
+                assert _on_feasibility_boundary(q, N, tin[pick[b]], band=1e-9), (batch, pick[b], out["status"][pick][b], ref["status"][b])
+        finally:
+            if path == "auto":
+                s.close()
 
 
 @pytest.mark.parametrize("batch,over", [(65536, dict()), (40001, dict()), (100, dict()), (65536, dict(z_ineq_hi=4.6))])
@@ -444,7 +473,7 @@ def test_bitwise_reproducible_across_launch_variants_of_one_path(q, batch):
 
 
 @pytest.mark.parametrize("sweep", [False, True])
-def test_one_launch_and_two_launch_forms_agree_bitwise(q, sweep, monkeypatch):
+def test_one_launch_and_two_launch_forms_agree_bitwise(q, O, sweep, monkeypatch):
     """A batch beyond the resident size takes ismpc_tick_quad_one: a wavefront that defers an instance (active vertical inequality rows)
     runs the fallback for it itself, on the instance's own parameter set in a sweep.  ISMPC_ONE_LAUNCH=0 is the two-launch form
     (ismpc_tick_quad + the deferred list + ismpc_tick_affine_fallback).  Same arithmetic: byte-identical records, also through ten
@@ -454,6 +483,7 @@ def test_one_launch_and_two_launch_forms_agree_bitwise(q, sweep, monkeypatch):
     B = 40000
     tin = workload.make_batch(100, B, seed=55)
     monkeypatch.setenv("ISMPC_ROLLOUT", "host")
+    sets = None
     if sweep:
         sets = workload.make_sweep_params(8, N=100)
         for p in sets:
@@ -470,9 +500,33 @@ def test_one_launch_and_two_launch_forms_agree_bitwise(q, sweep, monkeypatch):
     monkeypatch.setenv("ISMPC_ONE_LAUNCH", "0")
     two = make()
     a, b = one.solve_batch(tin), two.solve_batch(tin)
+    ia, ib = one.launch_info(), two.launch_info()
+    assert (ia["family"], ia["lanes"], ia["kernels"], ia["sweep"]) == ("quad_one", 8, 1, sweep), ia
+    assert (ib["family"], ib["lanes"], ib["kernels"], ib["sweep"]) == ("quad", 8, 2, sweep), ib
     act = (a["status"] & q.ST_Z_INEQ_ACTIVE) != 0
     assert act.sum() > 100 and ((a["status"] & q.ST_Z_FAILED) == 0).all()
     assert a.tobytes() == b.tobytes()
+    # both forms against the oracle (one per parameter set in a sweep) on 192 instances fixed beforehand
+    pick = np.sort(np.random.default_rng(B).choice(B, 192, replace=False))
+    n_act = 0
+    for k in range(8 if sweep else 1):
+        mine = pick[tin["reserved"][pick] == k] if sweep else pick
+        over = dict(z_ineq_hi=4.6)
+        if sweep:
+            over.update(mass=sets[k].mass, h_des=sets[k].h_des, q_p=sets[k].q_p, q_u=sets[k].q_u, q_v=sets[k].q_v, foot_width=sets[k].foot_width)
+        ref, _ = O.Oracle(O.default_params(100, **over)).solve(tin[mine])
+        n_act += int(((ref["status"] & q.ST_Z_INEQ_ACTIVE) != 0).sum())
+        for rec in (a, b):
+            o = rec[mine]
+            assert (((o["status"] ^ ref["status"]) & q.ST_Z_INEQ_ACTIVE) == 0).all()
+            assert_parity(q, o, ref)
+            for i in np.where(o["status"] != ref["status"])[0]:      # the rule of test_against_oracle_seeded
+                assert ((o["status"][i] ^ ref["status"][i]) & ~(q.ST_X_INFEASIBLE | q.ST_Y_INFEASIBLE)) == 0
+                assert _on_feasibility_boundary(q, 100, tin[mine[i]], band=1e-9, **over), (k, mine[i], o["status"][i], ref["status"][i])
+    print(f"oracle sample: 192 instances, {n_act} with active vertical inequality rows")
+    # z_ineq_hi = 4.6 makes the upper rows active on most of the batch (the oracle alone, first 4 000 instances: 0.85 plain, 0.85 over the
+    # eight sets): the sample does go through the deferred paths
+    assert n_act >= 96, n_act
     sa, sb = q.to_device(tin), q.to_device(tin)
     ta = one.rollout_torch(sa, int(tin["simulation_time"].max()) + 1, 10); tb = two.rollout_torch(sb, int(tin["simulation_time"].max()) + 1, 10)
     torch.cuda.synchronize()
