@@ -95,7 +95,8 @@ typedef struct ismpc_tick_in {
     int32_t mpc_iter;          /* WalkState::mpcIter         types.hpp:80                   */
     int32_t control_iter;      /* WalkState::controlIter                                    */
     int32_t footstep_counter;  /* WalkState::footstepCounter                                */
-    int32_t reserved;          /* parameter set of the instance (ismpc_create_sweep); 0 otherwise */
+    int32_t reserved;          /* parameter set of the instance (ismpc_create_sweep), ISMPC_RESERVED(set, plan) on a
+                                  multi-plan handle (ismpc_create_plans); 0 otherwise */
 } ismpc_tick_in;               /* 72 bytes */
 
 typedef struct ismpc_tick_out {
@@ -144,6 +145,27 @@ int ismpc_sweep_info(const ismpc_handle* h, int* n_sets, int* newton_iterations,
  * does for one set): rel_err[t] = max |device - host| / max |host| for t = 0 H^-1, 1 affine tables of the vertical stage,
  * 2 W_p, 3 S W_p, 4 Hinv S', 5 S Hinv S', 6 anticipative tails, 7 the lane-group layout of 1.  rel_err: 8 doubles.   */
 int ismpc_sweep_verify_tables(ismpc_handle* h, int set, double* rel_err);
+
+/* MULTI-PLAN HANDLES.  The instances of a batch may also walk different FOOTSTEP PLANS (direction, stride, stance width, step
+ * timing): n_plans footstep plans (ftsp: n_plans x rows x 4, row-major, each as ismpc_create takes it) and n_sets parameter
+ * sets in ONE handle; an instance names both in ismpc_tick_in.reserved -- low 16 bits the set, high bits the plan.  A set >= n_sets,
+ * a plan >= n_plans or a negative value: ISMPC_ST_BAD_INDEX, state passed through (the sweep's rule).
+ * 1 <= n_plans <= 32767, 1 <= n_sets <= 65535 (and n_sets x n_plans <= 2^24: every pair has its own anticipative tails, 16 bytes per
+ * midpoint row).  The sets share what a sweep's sets share.  All plans have the same `rows`; x, y and t are free per plan; the z column
+ * must be bit-identical across the plans (ISMPC_E_UNSUPPORTED otherwise): plans off z = 0 that share one height profile work, with
+ * one set of offset tables per parameter set.  ISMPC_PATH=dense: ISMPC_E_UNSUPPORTED.  Argument errors are reported before the device
+ * is touched.
+ * n_sets == 1: every table comes from the host's long-double build that ismpc_create does, per plan, tails included -- an instance's
+ * record is byte-identical to a plain handle created on that plan (within one lane layout).  n_sets > 1: the sets' tables are built
+ * on the device exactly as ismpc_create_sweep builds them, the tails for every (set, plan) pair (eta belongs to the set).
+ * Every entry point below works on such a handle; ismpc_sweep_bind sorts by (set, plan) pair, ismpc_sweep_info reports n_sets,
+ * ismpc_get_midpoint returns plan 0.                                                                                           */
+int ismpc_create_plans(const ismpc_params* params, int n_sets, const double* ftsp, int n_plans, int rows,
+                       int device, ismpc_handle** out);
+#define ISMPC_RESERVED(set, plan)  ((int32_t)(((uint32_t)(plan) << 16) | (uint32_t)(set)))
+int ismpc_plans_info(const ismpc_handle* h, int* n_plans);                 /* 1 for every other handle */
+/* ismpc_get_midpoint of one plan of the handle (0 <= plan < n_plans). */
+int ismpc_get_midpoint_plan(const ismpc_handle* h, int plan, double* dst, int capacity_rows);
 
 void ismpc_destroy(ismpc_handle* h);
 
@@ -223,7 +245,7 @@ int         ismpc_fallback_counters(ismpc_handle* h, int* out4);
 /* Which kernel the handle's most recent step (ismpc_solve_batch*) or closed loop (ismpc_rollout_device) enqueued, as the host
  * recorded it where it launched (no device work, no synchronisation): out8 = { kernel family (ISMPC_KERNEL_*), lanes per
  * instance, R = horizon samples per lane, RW = samples per lane of the inequality fallback's one-instance-per-wavefront body,
- * 1 for the parameter-sweep instantiation, kernels enqueued per step (2 = tick + fallback launch, rollout + resume launch),
+ * bit 0 (1) for the parameter-sweep instantiation and bit 1 (2) for the multi-plan one (3: several sets x several plans), kernels enqueued per step (2 = tick + fallback launch, rollout + resume launch),
  * batch, 1 when the ismpc_sweep_bind order placed the instances }.  All zero before the first launch; a closed loop run as
  * one launch per tick (ISMPC_ROLLOUT=host, N > 128) reports its last tick.                                              */
 #define ISMPC_KERNEL_NONE         0

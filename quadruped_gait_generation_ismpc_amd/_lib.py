@@ -33,7 +33,7 @@ EXPORTS = ["ismpc_params_default", "ismpc_create", "ismpc_destroy", "ismpc_solve
            "ismpc_get_params", "ismpc_midpoint_rows", "ismpc_get_midpoint", "ismpc_set_timing",
            "ismpc_last_kernel_ms", "ismpc_reserve", "ismpc_host_alloc", "ismpc_host_free", "ismpc_host_register",
            "ismpc_host_unregister", "ismpc_create_sweep", "ismpc_sweep_info", "ismpc_sweep_verify_tables", "ismpc_fallback_counters", "ismpc_sweep_bind",
-           "ismpc_last_launch_info"]
+           "ismpc_last_launch_info", "ismpc_create_plans", "ismpc_plans_info", "ismpc_get_midpoint_plan"]
 
 _lib = None
 
@@ -84,6 +84,9 @@ def load():
     lib.ismpc_fallback_counters.argtypes = [vp, vp]; lib.ismpc_fallback_counters.restype = ci
     lib.ismpc_sweep_bind.argtypes = [vp, ci, vp, vp]; lib.ismpc_sweep_bind.restype = ci
     lib.ismpc_last_launch_info.argtypes = [vp, vp]; lib.ismpc_last_launch_info.restype = ci
+    lib.ismpc_create_plans.argtypes = [vp, ci, vp, ci, ci, ci, C.POINTER(vp)]; lib.ismpc_create_plans.restype = ci
+    lib.ismpc_plans_info.argtypes = [vp, C.POINTER(ci)]; lib.ismpc_plans_info.restype = ci
+    lib.ismpc_get_midpoint_plan.argtypes = [vp, ci, vp, ci]; lib.ismpc_get_midpoint_plan.restype = ci
     _lib = lib
     return lib
 

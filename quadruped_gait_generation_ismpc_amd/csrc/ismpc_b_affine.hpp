@@ -597,7 +597,7 @@ __device__ __forceinline__ void tick_affine_body(const DevConst& c, const int gi
 #endif
 // SW: a parameter-sweep handle at a horizon the lane-group kernels do not cover (128 < N <= 256): one instance per wavefront, so the
 // instance's parameter set is wave-uniform and the body runs on that set's own record (tables and scalars), as the fallback launch does.
-template <int R, bool SW = false>
+template <int R, int SW = 0>
 __global__ __launch_bounds__(64 * ISMPC_AFF_WAVES) __attribute__((amdgpu_num_sgpr(80)))
 void ismpc_tick_affine(const DevConst c, const ismpc_tick_in* __restrict__ in_ro, ismpc_tick_in* state_rw,
                        ismpc_tick_out* __restrict__ out, double* __restrict__ u_traj, int batch, int rollout_frame,
@@ -607,8 +607,9 @@ void ismpc_tick_affine(const DevConst c, const ismpc_tick_in* __restrict__ in_ro
     const int gi = blockIdx.x * ISMPC_AFF_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (gi >= batch) return;
     if constexpr (SW) {
-        const int ps = __builtin_amdgcn_readfirstlane((((rollout_frame >= 0) ? state_rw : in_ro) + gi)->reserved);
-        const bool known = ps >= 0 && ps < c.nsets;                  // an unknown set: ISMPC_ST_BAD_INDEX, state passed through
+        int ps = __builtin_amdgcn_readfirstlane((((rollout_frame >= 0) ? state_rw : in_ro) + gi)->reserved);
+        if constexpr (SW == 2) ps = record_index<2>(c, ps);          // (a multi-plan handle: the record of the instance's (set, plan) pair)
+        const bool known = ps >= 0 && ps < c.nsets * (SW == 2 ? c.nplans : 1);   // an unknown set: ISMPC_ST_BAD_INDEX, state passed through
         tick_affine_body<R, false>(c.sets[known ? ps : 0], gi, lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id,
                                    zmark ? zlist_of(zmark, batch) : nullptr, batch, nullptr, known ? 0 : ISMPC_ST_BAD_INDEX);
     } else
@@ -616,7 +617,7 @@ void ismpc_tick_affine(const DevConst c, const ismpc_tick_in* __restrict__ in_ro
 }
 
 // Second launch of every tick of a large batch: exits at once unless the first one deferred instances (active inequality rows).
-template <int R, bool SW = false>
+template <int R, int SW = 0>
 __global__ __launch_bounds__(256)
 void ismpc_tick_affine_fallback(const DevConst c, const ismpc_tick_in* __restrict__ in_ro, ismpc_tick_in* state_rw,
                                 ismpc_tick_out* __restrict__ out, double* __restrict__ u_traj, int batch, int rollout_frame,
@@ -635,7 +636,8 @@ void ismpc_tick_affine_fallback(const DevConst c, const ismpc_tick_in* __restric
         {
             if (SW) {
                 // one instance per wavefront: its parameter set is wave-uniform, the body runs on that set's own record
-                const int ps = __builtin_amdgcn_readfirstlane((((rollout_frame >= 0) ? state_rw : in_ro) + gi)->reserved);
+                int ps = __builtin_amdgcn_readfirstlane((((rollout_frame >= 0) ? state_rw : in_ro) + gi)->reserved);
+                if constexpr (SW == 2) ps = record_index<2>(c, ps);
                 tick_affine_body<R, true>(c.sets[ps], gi, lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id, nullptr, 0, zwin);    // (a deferred instance has a valid set)
             } else tick_affine_body<R, true>(c, gi, lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id, nullptr, 0, zwin);
         }

@@ -25,6 +25,9 @@ struct DevConst {
     const double *HSt, *SHSt;
     const DevConst* sets; int nsets;  // parameter sweeps (ismpc_create_sweep): one record per parameter set, its own tables and scalars; the
                                       // instance's record names its set (ismpc_tick_in.reserved).  NULL / 0 for a plain handle
+    int nplans;                       // multi-plan handles (ismpc_create_plans): `sets` holds one record per (set, plan) PAIR, set-major -- the set's
+                                      // record with the plan's midpoint tables, step timings and the pair's tails -- and reserved is
+                                      // ISMPC_RESERVED(set, plan).  0 otherwise
     const int* order;                 // sweeps, after ismpc_sweep_bind: the instances of the bound batch sorted by parameter set.  Slot g of the
                                       // launch runs instance order[g], so the lane groups of a wavefront read ONE set's tables, and workgroup b
                                       // takes the slots of virtual block sweep_vblock(b): the workgroups an XCD receives (b mod 8) cover one
@@ -97,14 +100,25 @@ __host__ __device__ inline size_t zscratch_bytes(int batch) { return 4 * (size_t
 __device__ __forceinline__ int* zlist_of(unsigned char* zmark, int) { return reinterpret_cast<int*>(zmark); }
 // Caller bookkeeping in front of solve(): Controller.cpp:297-304 (enabled) and :310.
 struct Walk { double sim; int mpc, ctl, fc; };
-__device__ __forceinline__ Walk load_walk(const DevConst& c, const ismpc_tick_in* rec, int rollout_frame)
+// (ftsp_t: the step timings of the instance's plan -- c.ftsp_t unless the lanes of a wavefront walk different plans)
+__device__ __forceinline__ Walk load_walk(const DevConst& c, const double* ftsp_t, const ismpc_tick_in* rec, int rollout_frame)
 {
     Walk w; w.sim = rec->simulation_time; w.mpc = rec->mpc_iter; w.ctl = rec->control_iter; w.fc = rec->footstep_counter;
     if (rollout_frame >= 0) {
-        if (w.fc >= 0 && w.fc < c.rows && w.sim >= c.ftsp_t[w.fc] - 1) { w.ctl = 0; w.mpc = 0; w.fc = w.fc + 1; }
+        if (w.fc >= 0 && w.fc < c.rows && w.sim >= ftsp_t[w.fc] - 1) { w.ctl = 0; w.mpc = 0; w.fc = w.fc + 1; }
         w.sim = (double)rollout_frame;
     }
     return w;
+}
+__device__ __forceinline__ Walk load_walk(const DevConst& c, const ismpc_tick_in* rec, int rollout_frame) { return load_walk(c, c.ftsp_t, rec, rollout_frame); }
+// SW, the compile-time form of a kernel: 0 = plain handle, 1 = parameter sweep, 2 = multi-plan handle.  The record in c.sets that
+// ismpc_tick_in.reserved names: the set (SW = 1) or the (set, plan) pair (SW = 2); -1 when it names none.
+template <int SW> __device__ __forceinline__ int record_index(const DevConst& c, int reserved)
+{
+    if constexpr (SW == 2) {
+        const int set = reserved & 0xffff, plan = reserved >> 16;
+        return (reserved >= 0 && set < c.nsets && plan < c.nplans) ? set * c.nplans + plan : -1;
+    } else return (reserved >= 0 && reserved < c.nsets) ? reserved : -1;
 }
 // 0 = run the tick, else the pass-through status (MPCSolver.cpp:214; index range of :259,381)
 __device__ __forceinline__ int gate_tick(const DevConst& c, const Walk& w, int& idx)
@@ -146,7 +160,7 @@ __device__ __forceinline__ unsigned long long stamp_now()
 
 // What one instance carries from tick to tick (group-uniform: every lane of the group holds the same values) and what a tick
 // produces (valid in lane 0 of the group).
-struct QState { double x, y, z, xd, yd, zd; Walk w; int ps; };     // ps: parameter set of the instance (sweep handles; -1 = invalid record)
+struct QState { double x, y, z, xd, yd, zd; Walk w; int ps; };     // ps: the instance's record in c.sets (sweep handles: its parameter set; multi-plan handles: its (set, plan) pair; -1 = invalid)
 struct QOut { double x, y, z, xd, yd, zd, uz0, ux0, uy0; int status, itx, ity; };
 
 __device__ __forceinline__ void store_record(ismpc_tick_out* __restrict__ rec, const QOut& o)

@@ -1,7 +1,7 @@
 // Formulation B, part 4 of 4 of the translation unit ismpc_hip.hip: the lane-group family, the default for horizons N <= 128.
 // Per-tick kernels ismpc_tick_quad (two-launch form, with ismpc_tick_affine_fallback behind it), ismpc_tick_quad_inline and
 // ismpc_tick_quad_one (one launch per step), the closed loop inside one launch (ismpc_rollout_quad), and the counting sort of
-// ismpc_sweep_bind (sweep_sort_*).
+// ismpc_sweep_bind (sweep_sort_*, plans_sort_*).
 #pragma once
 #include "ismpc_b_affine.hpp"
 
@@ -174,8 +174,10 @@ template <int R, int LPI> constexpr int wave_lds_double2_fb() { return wave_lds_
 #endif
 // SW: parameter sweep -- the groups of a wavefront may belong to different parameter sets: what depends on the set (tables
 // of the vertical stage, tails, mass, eta, box widths, bounds on S u) is read through the instance's own record c.sets[s.ps]
-// (per-lane loads); horizon, plan, dt, g and the gate are the handle's.  SW = false compiles to exactly the plain kernel.
-template <int R, int LPI, int KF, bool SW = false>
+// (per-lane loads); horizon, plan, dt, g and the gate are the handle's.  SW = 0 compiles to exactly the plain kernel.
+// SW = 2: multi-plan handle -- the record is the one of the instance's (set, plan) pair, and the plan is read through it too: the
+// midpoint window (the same coalesced load from another base address), the tails and, in the callers, the step timings.
+template <int R, int LPI, int KF, int SW = 0>
 __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lane, const QState& s, QOut& o, double* __restrict__ u_traj_inst,
                                                 double2* __restrict__ lds_wave)
 {
@@ -192,6 +194,7 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
     const double p_half_run = SW ? P->half_run : c.half_run, p_half_first = SW ? P->half_first : c.half_first;
     const double* p_tailx = SW ? P->tailx : c.tailx; const double* p_taily = SW ? P->taily : c.taily;
     const double p_dt_over_mass = SW ? P->dt_over_mass : c.dt_over_mass, p_h_des = SW ? P->h_des : c.h_des;
+    const double* p_midxy = SW == 2 ? P->midxy : c.midxy;
     int idx;
     const int gate_status = gate_tick(c, w, idx) | ((SW && s.ps < 0) ? ISMPC_ST_BAD_INDEX : 0);     // group-uniform; a gated group runs the arithmetic on idx = 0 and drops it
     int status = gate_status;
@@ -210,7 +213,7 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
 #pragma unroll
     for (int k = 0; k < R; ++k) {
         const int j = k * LPI + li;
-        Lm[(j / R) * MIDM + (j % R)] = reinterpret_cast<const double2*>(c.midxy)[min(idx + j, c.nmid - 1)];
+        Lm[(j / R) * MIDM + (j % R)] = reinterpret_cast<const double2*>(p_midxy)[min(idx + j, c.nmid - 1)];
     }
     double u[R], su[R];
     double smin = INFINITY, smax = -INFINITY;
@@ -466,8 +469,10 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
                 double vx = 0.0, vy = 0.0;
                 if (stage3) {
                     const double sa = (a[r] < 0.0) ? -1.0 : 1.0;
-                    vx = fma(sgx * sa, (fabs(a[r]) > 0.0) ? fmin(tau[0] * fabs(a[r]), h) : 0.0, c.midx[idx + n]);
-                    vy = fma(sgy * sa, (fabs(a[r]) > 0.0) ? fmin(tau[1] * fabs(a[r]), h) : 0.0, c.midy[idx + n]);
+                    // (SW = 2: the plan's midpoints from the staged window -- the same values, and the pair's record need not stay live)
+                    const double2 mq = SW == 2 ? Lm[li * MIDM + r] : make_double2(c.midx[idx + n], c.midy[idx + n]);
+                    vx = fma(sgx * sa, (fabs(a[r]) > 0.0) ? fmin(tau[0] * fabs(a[r]), h) : 0.0, mq.x);
+                    vy = fma(sgy * sa, (fabs(a[r]) > 0.0) ? fmin(tau[1] * fabs(a[r]), h) : 0.0, mq.y);
                 }
                 u_traj_inst[n] = run ? u[r] : 0.0; u_traj_inst[N + n] = vx; u_traj_inst[2 * N + n] = vy;
             }
@@ -477,7 +482,7 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
 }
 
 // One launch = one tick: record in, record out (and, in the host-driven closed loop, state fed back in place)
-template <int R, int LPI, int KF, bool SW = false>
+template <int R, int LPI, int KF, int SW = 0>
 __device__ __forceinline__ bool tick_group_body(const DevConst& c, const int gi_raw, const int batch, const int lane,
                                                 const ismpc_tick_in* __restrict__ in_ro, ismpc_tick_in* state_rw,
                                                 ismpc_tick_out* __restrict__ out, double* __restrict__ u_traj,
@@ -489,11 +494,16 @@ __device__ __forceinline__ bool tick_group_body(const DevConst& c, const int gi_
     STAMP(0);                                         // first instructions of the wavefront
     const ismpc_tick_in* rec = ((rollout_frame >= 0) ? state_rw : in_ro) + gi;
     QState s;
-    s.w = load_walk(c, rec, rollout_frame);
+    if constexpr (SW == 2) {                          // the instance's pair first: the caller bookkeeping runs on ITS plan's step timings
+        s.ps = record_index<2>(c, rec->reserved);
+        s.w = load_walk(c, c.sets[max(s.ps, 0)].ftsp_t, rec, rollout_frame);
+    } else s.w = load_walk(c, rec, rollout_frame);
     s.x = rec->com_pos[0]; s.y = rec->com_pos[1]; s.z = rec->com_pos[2];
     s.xd = rec->com_vel[0]; s.yd = rec->com_vel[1]; s.zd = rec->com_vel[2];
-    s.ps = 0;
-    if (SW) { const int ps = rec->reserved; s.ps = (ps >= 0 && ps < c.nsets) ? ps : -1; }       // an unknown set: ISMPC_ST_BAD_INDEX, state passed through
+    if constexpr (SW != 2) {
+        s.ps = 0;
+        if (SW) { const int ps = rec->reserved; s.ps = (ps >= 0 && ps < c.nsets) ? ps : -1; }   // an unknown set: ISMPC_ST_BAD_INDEX, state passed through
+    }
     QOut o;
     const bool deferred = tick_group_core<R, LPI, KF, SW>(c, lane, s, o, (u_traj && valid) ? u_traj + (size_t)gi * 3 * c.N : nullptr, lds_wave);
     if ((lane & (LPI - 1)) == 0 && valid) {
@@ -519,12 +529,12 @@ __device__ __forceinline__ int sweep_vblock(int b, int nb)
     return x * q + min(x, r) + (b >> 3);
 }
 // instance of launch slot `slot` (see DevConst::order); slots past the batch name no instance
-template <bool SW> __device__ __forceinline__ int slot_instance(const DevConst& c, int slot, int batch)
+template <int SW> __device__ __forceinline__ int slot_instance(const DevConst& c, int slot, int batch)
 {
     if (SW) { if (c.order) return slot < batch ? c.order[slot] : batch; }
     return slot;
 }
-template <int R, int LPI, bool SW = false>
+template <int R, int LPI, int SW = 0>
 __global__ __launch_bounds__(64 * ISMPC_QUAD_WAVES)
 void ismpc_tick_quad(const DevConst c, const ismpc_tick_in* __restrict__ in_ro, ismpc_tick_in* state_rw,
                      ismpc_tick_out* __restrict__ out, double* __restrict__ u_traj, int batch, int rollout_frame,
@@ -569,13 +579,13 @@ void ismpc_tick_quad_inline(const DevConst c, const ismpc_tick_in* __restrict__ 
 // (the kernel asks for them, and the compiler hands that register budget down to the fallback it calls: the fallback spills to
 // scratch instead, and only a wavefront that defers an instance runs it).  No second, normally idle, launch per step: +1-2 % at
 // 65 536 instances, +4 % at 32 768, +8 % at 16 384 (same box, scripts/ab_env.sh ISMPC_ONE_LAUNCH=0).  SW: parameter sweeps, the
-// fallback runs on the deferred instance's own set.
+// fallback runs on the deferred instance's own set (SW = 2, multi-plan handles: on the record of its (set, plan) pair).
 // wavefronts per SIMD of ismpc_tick_quad<R, LPI, SW> (profiles/r03/kernel_resources.md): what the one-launch form asks for
 #ifndef ISMPC_OCC_R13
 #define ISMPC_OCC_R13 2
 #endif
-template <int R, bool SW> constexpr int one_occ() { return R <= 4 ? (SW ? 3 : 4) : R <= 7 ? 3 : R == 8 ? (SW ? 2 : 3) : R <= 13 ? ISMPC_OCC_R13 : 1; }
-template <int R, int LPI, int RW, bool SW>
+template <int R, int SW> constexpr int one_occ() { return R <= 4 ? (SW ? 3 : 4) : R <= 7 ? 3 : R == 8 ? (SW ? 2 : 3) : R <= 13 ? ISMPC_OCC_R13 : 1; }
+template <int R, int LPI, int RW, int SW>
 __global__ __launch_bounds__(64 * ISMPC_QUAD_WAVES, (one_occ<R, SW>()))
 void ismpc_tick_quad_one(const DevConst c, const ismpc_tick_in* __restrict__ in_ro, ismpc_tick_in* state_rw,
                          ismpc_tick_out* __restrict__ out, double* __restrict__ u_traj, int batch, int rollout_frame,
@@ -596,7 +606,8 @@ void ismpc_tick_quad_one(const DevConst c, const ismpc_tick_in* __restrict__ in_
         if ((m >> (LPI * q)) & 1ull) {
             const int gi = __builtin_amdgcn_readfirstlane(slot_instance<SW>(c, wave * IPW + q, batch));
             const DevConst* cp = cdev;
-            if (SW) cp = c.sets + __builtin_amdgcn_readfirstlane((((rollout_frame >= 0) ? state_rw : in_ro) + gi)->reserved);   // (a deferred instance has a valid set)
+            if (SW == 1) cp = c.sets + __builtin_amdgcn_readfirstlane((((rollout_frame >= 0) ? state_rw : in_ro) + gi)->reserved);   // (a deferred instance has a valid set)
+            if (SW == 2) cp = c.sets + __builtin_amdgcn_readfirstlane(record_index<2>(c, (((rollout_frame >= 0) ? state_rw : in_ro) + gi)->reserved));
             fallback_call_one<RW, one_occ<R, SW>()>(cp, gi, lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id, reinterpret_cast<double*>(lds_mid[wv]));
         }
 }
@@ -610,7 +621,7 @@ void ismpc_tick_quad_one(const DevConst c, const ismpc_tick_in* __restrict__ in_
 //   FB = true (second launch, exits at once unless the first one parked something): one wavefront per parked instance
 //     resumes it at its tick, running the active-set fallback (all 64 lanes, through memory) at the ticks that need it.
 // Keeping the fallback out of the first kernel keeps its register budget that of the tick itself.
-template <int R, int LPI, int RW, bool FB, bool SW = false>
+template <int R, int LPI, int RW, bool FB, int SW = 0>
 __global__ __launch_bounds__(64 * ISMPC_QUAD_WAVES, 2)
 void ismpc_rollout_quad(const DevConst c, ismpc_tick_in* state, ismpc_tick_out* __restrict__ traj, int batch, int first_frame, int ticks,
                         int* __restrict__ stop_tick, int launch_id)
@@ -633,14 +644,15 @@ void ismpc_rollout_quad(const DevConst c, ismpc_tick_in* state, ismpc_tick_out* 
         s.w.sim = rec->simulation_time; s.w.mpc = rec->mpc_iter; s.w.ctl = rec->control_iter; s.w.fc = rec->footstep_counter;
         s.x = rec->com_pos[0]; s.y = rec->com_pos[1]; s.z = rec->com_pos[2];
         s.xd = rec->com_vel[0]; s.yd = rec->com_vel[1]; s.zd = rec->com_vel[2]; s.ps = 0;
-        if (SW) { const int ps = rec->reserved; s.ps = (ps >= 0 && ps < c.nsets) ? ps : -1; }     // sweep handles: the instance's parameter set
+        if (SW) s.ps = record_index<SW>(c, rec->reserved);             // sweep handles: the instance's parameter set; multi-plan handles: its (set, plan) pair
+        const double* ftsp_t = SW == 2 ? c.sets[max(s.ps, 0)].ftsp_t : c.ftsp_t;
         bool alive = true;                                              // FB = false: false once the instance is parked
         int stopped = -1;
         for (int t = t0; t < ticks; ++t) {
             const int frame = first_frame + t;
             // caller bookkeeping in front of solve(): Controller.cpp:297-304 (enabled) and :310 -- load_walk's rollout branch
             const Walk before = s.w;
-            if (s.w.fc >= 0 && s.w.fc < c.rows && s.w.sim >= c.ftsp_t[s.w.fc] - 1) { s.w.ctl = 0; s.w.mpc = 0; s.w.fc = s.w.fc + 1; }
+            if (s.w.fc >= 0 && s.w.fc < c.rows && s.w.sim >= ftsp_t[s.w.fc] - 1) { s.w.ctl = 0; s.w.mpc = 0; s.w.fc = s.w.fc + 1; }
             s.w.sim = (double)frame;
             QOut o;
             const bool def = tick_group_core<R, LPI, ISMPC_KF_ROLLOUT, SW>(c, lane, s, o, nullptr, lds_mid[wv]);
@@ -700,7 +712,7 @@ __global__ __launch_bounds__(256) void sweep_sort_hist(const ismpc_tick_in* __re
     const int ps = in[i].reserved;
     atomicAdd(counts + ((ps >= 0 && ps < nsets) ? ps : nsets), 1);
 }
-// exclusive scan of counts[0 .. n) in place (one workgroup; n <= 65 536 + 1): counts[k] becomes the first slot of bucket k
+// exclusive scan of counts[0 .. n) in place (one workgroup; n <= 65 536 + 1 sets, or 2^24 + 1 (set, plan) pairs of a multi-plan handle): counts[k] becomes the first slot of bucket k
 __global__ __launch_bounds__(256) void sweep_sort_scan(int* __restrict__ counts, int n)
 {
     __shared__ int part[256];
@@ -720,6 +732,22 @@ __global__ __launch_bounds__(256) void sweep_sort_scatter(const ismpc_tick_in* _
     if (i >= batch) return;
     const int ps = in[i].reserved;
     order[atomicAdd(cursor + ((ps >= 0 && ps < nsets) ? ps : nsets), 1)] = i;      // (the order INSIDE a bucket is whatever the atomics give: no result depends on it)
+}
+// ... and of a multi-plan handle by (set, plan) pair, set-major (bucket nsets x nplans: records that name no pair): the lane groups of a
+// wavefront then read one set's tables AND one plan's window
+__global__ __launch_bounds__(256) void plans_sort_hist(const DevConst c, const ismpc_tick_in* __restrict__ in, int batch, int* __restrict__ counts)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= batch) return;
+    const int pr = record_index<2>(c, in[i].reserved);
+    atomicAdd(counts + (pr >= 0 ? pr : c.nsets * c.nplans), 1);
+}
+__global__ __launch_bounds__(256) void plans_sort_scatter(const DevConst c, const ismpc_tick_in* __restrict__ in, int batch, int* __restrict__ cursor, int* __restrict__ order)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= batch) return;
+    const int pr = record_index<2>(c, in[i].reserved);
+    order[atomicAdd(cursor + (pr >= 0 ? pr : c.nsets * c.nplans), 1)] = i;
 }
 
 }  // namespace

@@ -23,7 +23,8 @@
 //   samples per lane     the smallest instantiated R that covers N (the shape table at quad_R())
 //   launch form          every wavefront resident at once (waves <= 8 per CU): ismpc_tick_quad_inline, one launch;
 //                        larger batches: ismpc_tick_quad_one, one launch, unless a recent launch deferred instances -- then
-//                        ismpc_tick_quad + ismpc_tick_affine_fallback; parameter sweeps: the SW instantiations of the latter two
+//                        ismpc_tick_quad + ismpc_tick_affine_fallback; parameter sweeps: the SW = 1 instantiations of the latter two,
+//                        multi-plan handles (ismpc_create_plans): their SW = 2 instantiations
 //   closed loops         ismpc_rollout_quad, the whole loop in one launch (ISMPC_ROLLOUT=host: one launch per tick)
 //
 // There is no CPU fallback in this file: every entry point needs a HIP device.
@@ -88,6 +89,9 @@ struct ismpc_handle {
     const double* vqT32 = nullptr; const double* tzgT32 = nullptr;
     const double* vqT8 = nullptr; const double* tzgT8 = nullptr;     // ... and 8 lanes per instance beyond LPI16_BATCH instances per launch
     const DevConst* sets8 = nullptr;                                  // sweep handles: the set records with the 8-lane tables (null: 16 lanes at every batch size)
+    const DevConst* sets32 = nullptr;                                 // multi-plan handles that choose the layout per launch: the pair records with the 32-lane tables
+    int nplans = 0;               // ismpc_create_plans: P footstep plans, c.sets = one record per (set, plan) pair; 0 for every other handle
+    std::vector<double> pl_midx, pl_midy;                             // ... and the host copy of every plan's midpoint columns (P x nmid each)
     bool kernel_rollout = true;   // closed loops run inside one launch (ismpc_rollout_quad); ISMPC_ROLLOUT=host: one launch per tick
     DevConst* c_dev = nullptr;    // the constants in device memory (the one-launch kernel's fallback call reads them there)
     bool sweep = false;           // ismpc_create_sweep: K parameter sets, tables built on the device (csrc/ismpc_sweep.hip)
@@ -184,8 +188,8 @@ int launch(ismpc_handle* h, int batch, const ismpc_tick_in* in, ismpc_tick_in* s
         hipLaunchKernelGGL(kernel, g, b, lds, s, c, in, state, out, u_traj, batch, rollout_frame, more...);
     };
     // what this step enqueues, for ismpc_last_launch_info: written where the kernel is launched, from the same shape values
-    auto note = [&](int family, int lanes, int r, int rw, bool sw, int kernels, bool ordered) {
-        const int v[8] = {family, lanes, r, rw, sw ? 1 : 0, kernels, batch, ordered ? 1 : 0};
+    auto note = [&](int family, int lanes, int r, int rw, int form, int kernels, bool ordered) {      // form: bit 0 = sweep, bit 1 = multi-plan instantiation
+        const int v[8] = {family, lanes, r, rw, form, kernels, batch, ordered ? 1 : 0};
         std::memcpy(h->last_launch, v, sizeof(v));
     };
     if (!h->dense_path) {
@@ -217,6 +221,31 @@ int launch(ismpc_handle* h, int batch, const ismpc_tick_in* in, ismpc_tick_in* s
             const int waves = (batch * lpi + 63) / 64;
             const dim3 qgrid((waves + ISMPC_QUAD_WAVES - 1) / ISMPC_QUAD_WAVES), qblock(64 * ISMPC_QUAD_WAVES);
             const DevConst* cdev = h->c_dev;
+            if (h->nplans) {
+                // multi-plan handle: the SW = 2 kernels read each instance's (set, plan) pair through c.sets, in the records of this launch's layout.
+                // The launch forms are a sweep's (one launch, or tick + fallback launch; never ismpc_tick_quad_inline); the lanes per instance are a
+                // plain handle's with one parameter set -- whose records are then byte-identical to a plain handle's on that plan -- and a sweep's
+                // with several
+                cq.sets = (lpi == 8 && h->sets8) ? h->sets8 : ((lpi == 32 && h->sets32) ? h->sets32 : h->c.sets);
+                if (h->sweep && lpi != 16 && lpi != 8) return fail(ISMPC_E_UNSUPPORTED, "parameter sweep: 16 or 8 lanes per instance");
+                cq.order = (h->order && h->order_batch == batch && rollout_frame < 0) ? h->order : nullptr;
+                const int form = 2 | (h->sweep ? 1 : 0);
+                quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
+                    if (one_big) {
+                        tick(ismpc_tick_quad_one<RR, LL, RW_, 2>, qgrid, qblock, 0, cq, zm, lid, cdev);
+                        note(ISMPC_KERNEL_QUAD_ONE, LL, RR, RW_, form, 1, cq.order != nullptr);
+                    } else {
+                        tick(ismpc_tick_quad<RR, LL, 2>, qgrid, qblock, 0, cq, zm, lid);
+                        note(ISMPC_KERNEL_QUAD, LL, RR, RW_, form, zm ? 2 : 1, cq.order != nullptr);
+                    }
+                });
+                if (!one_big && zm) {
+                    if (R == 1) tick(ismpc_tick_affine_fallback<1, 2>, fgrid, block, 0, h->c, zm, lid);
+                    else        tick(ismpc_tick_affine_fallback<2, 2>, fgrid, block, 0, h->c, zm, lid);
+                }
+                HIP_TRY(hipGetLastError());
+                return ISMPC_OK;
+            }
             if (h->sweep) {
                 // parameter sweep: the per-tick kernel reads each instance's set through c.sets (16 lanes per instance, 8 beyond LPI16_BATCH)
                 if (lpi == 8) cq.sets = h->sets8;
@@ -226,8 +255,8 @@ int launch(ismpc_handle* h, int batch, const ismpc_tick_in* in, ismpc_tick_in* s
                 if (one_big) {
                     quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
                         if constexpr (LL != 32) {
-                            tick(ismpc_tick_quad_one<RR, LL, RW_, true>, qgrid, qblock, 0, cq, zm, lid, cdev);
-                            note(ISMPC_KERNEL_QUAD_ONE, LL, RR, RW_, true, 1, cq.order != nullptr);
+                            tick(ismpc_tick_quad_one<RR, LL, RW_, 1>, qgrid, qblock, 0, cq, zm, lid, cdev);
+                            note(ISMPC_KERNEL_QUAD_ONE, LL, RR, RW_, 1, 1, cq.order != nullptr);
                         }
                     });
                     HIP_TRY(hipGetLastError());
@@ -235,13 +264,13 @@ int launch(ismpc_handle* h, int batch, const ismpc_tick_in* in, ismpc_tick_in* s
                 }
                 quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
                     if constexpr (LL != 32) {
-                        tick(ismpc_tick_quad<RR, LL, true>, qgrid, qblock, 0, cq, zm, lid);
-                        note(ISMPC_KERNEL_QUAD, LL, RR, RW_, true, zm ? 2 : 1, cq.order != nullptr);
+                        tick(ismpc_tick_quad<RR, LL, 1>, qgrid, qblock, 0, cq, zm, lid);
+                        note(ISMPC_KERNEL_QUAD, LL, RR, RW_, 1, zm ? 2 : 1, cq.order != nullptr);
                     }
                 });
                 if (zm) {
-                    if (R == 1) tick(ismpc_tick_affine_fallback<1, true>, fgrid, block, 0, h->c, zm, lid);
-                    else        tick(ismpc_tick_affine_fallback<2, true>, fgrid, block, 0, h->c, zm, lid);
+                    if (R == 1) tick(ismpc_tick_affine_fallback<1, 1>, fgrid, block, 0, h->c, zm, lid);
+                    else        tick(ismpc_tick_affine_fallback<2, 1>, fgrid, block, 0, h->c, zm, lid);
                 }
                 HIP_TRY(hipGetLastError());
                 return ISMPC_OK;
@@ -250,22 +279,22 @@ int launch(ismpc_handle* h, int batch, const ismpc_tick_in* in, ismpc_tick_in* s
             if (zm && h->one_launch >= 1 && h->cus > 0 && waves <= 8 * h->cus) {
                 quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
                     tick(ismpc_tick_quad_inline<RR, LL, RW_>, qgrid, qblock, 0, cq, zm, lid, cdev);
-                    note(ISMPC_KERNEL_QUAD_INLINE, LL, RR, RW_, false, 1, false);
+                    note(ISMPC_KERNEL_QUAD_INLINE, LL, RR, RW_, 0, 1, false);
                 });
                 HIP_TRY(hipGetLastError());
                 return ISMPC_OK;
             }
             if (one_big) {                  // any other batch size: one launch too, at the tick's own three wavefronts per SIMD
                 quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
-                    tick(ismpc_tick_quad_one<RR, LL, RW_, false>, qgrid, qblock, 0, cq, zm, lid, cdev);
-                    note(ISMPC_KERNEL_QUAD_ONE, LL, RR, RW_, false, 1, false);
+                    tick(ismpc_tick_quad_one<RR, LL, RW_, 0>, qgrid, qblock, 0, cq, zm, lid, cdev);
+                    note(ISMPC_KERNEL_QUAD_ONE, LL, RR, RW_, 0, 1, false);
                 });
                 HIP_TRY(hipGetLastError());
                 return ISMPC_OK;
             }
             quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
                 tick(ismpc_tick_quad<RR, LL>, qgrid, qblock, 0, cq, zm, lid);
-                note(ISMPC_KERNEL_QUAD, LL, RR, RW_, false, zm ? 2 : 1, false);
+                note(ISMPC_KERNEL_QUAD, LL, RR, RW_, 0, zm ? 2 : 1, false);
             });
             if (zm) {
                 if (R == 1) tick(ismpc_tick_affine_fallback<1>, fgrid, block, 0, h->c, zm, lid);
@@ -276,14 +305,17 @@ int launch(ismpc_handle* h, int batch, const ismpc_tick_in* in, ismpc_tick_in* s
         }
         const dim3 agrid((batch + ISMPC_AFF_WAVES - 1) / ISMPC_AFF_WAVES), ablock(64 * ISMPC_AFF_WAVES);
         auto affine = [&](auto RR) {
-            if (h->sweep) {
-                tick(ismpc_tick_affine<RR, true>, agrid, ablock, 0, h->c, zm, lid);
-                if (zm) tick(ismpc_tick_affine_fallback<RR, true>, fgrid, block, 0, h->c, zm, lid);
+            if (h->nplans) {
+                tick(ismpc_tick_affine<RR, 2>, agrid, ablock, 0, h->c, zm, lid);
+                if (zm) tick(ismpc_tick_affine_fallback<RR, 2>, fgrid, block, 0, h->c, zm, lid);
+            } else if (h->sweep) {
+                tick(ismpc_tick_affine<RR, 1>, agrid, ablock, 0, h->c, zm, lid);
+                if (zm) tick(ismpc_tick_affine_fallback<RR, 1>, fgrid, block, 0, h->c, zm, lid);
             } else {
                 tick(ismpc_tick_affine<RR>, agrid, ablock, 0, h->c, zm, lid);
                 if (zm) tick(ismpc_tick_affine_fallback<RR>, fgrid, block, 0, h->c, zm, lid);
             }
-            note(ISMPC_KERNEL_AFFINE, 64, RR, RR, h->sweep, zm ? 2 : 1, false);
+            note(ISMPC_KERNEL_AFFINE, 64, RR, RR, (h->sweep ? 1 : 0) | (h->nplans ? 2 : 0), zm ? 2 : 1, false);
         };
         if (!wave_shape(R, affine)) return fail(ISMPC_E_UNSUPPORTED, "horizon N > 256");
         HIP_TRY(hipGetLastError());
@@ -297,7 +329,7 @@ int launch(ismpc_handle* h, int batch, const ismpc_tick_in* in, ismpc_tick_in* s
         if (waves == 16)     tick(ismpc_tick_dense<RR, 16>, grid, dim3(64 * 16), lds, h->c);
         else if (waves == 8) tick(ismpc_tick_dense<RR, 8>, grid, dim3(64 * 8), lds, h->c);
         else                 tick(ismpc_tick_dense<RR, 4>, grid, dim3(64 * 4), lds, h->c);
-        note(ISMPC_KERNEL_DENSE, 64, RR, 0, false, 1, false);
+        note(ISMPC_KERNEL_DENSE, 64, RR, 0, 0, 1, false);
     };
     if (!wave_shape(R, dense)) return fail(ISMPC_E_UNSUPPORTED, "horizon N > 256");
     HIP_TRY(hipGetLastError());
@@ -328,10 +360,25 @@ void ismpc_params_default(ismpc_params* p)
     p->lambda_gate = 2.0;                                   // MPCSolver.cpp:322
 }
 
-static int create_impl(const ismpc_params* params, int K, bool sweep, const double* ftsp, int rows, int device, ismpc_handle** out)
+// P: footstep plans of a multi-plan handle (ftsp: P x rows x 4; the handle's own tables come from plan 0), 0 for every other handle
+static int create_impl(const ismpc_params* params, int K, bool sweep, const double* ftsp, int rows, int device, ismpc_handle** out, int P = 0)
 {
     if (!params || !ftsp || !out) return fail(ISMPC_E_INVALID, "null argument");
     *out = nullptr;
+    if (P) {
+        // everything that can be said about the arguments is said before the device is touched
+        if (P < 1 || P > 32767) return fail(ISMPC_E_INVALID, "a multi-plan handle holds 1 .. 32767 footstep plans");
+        if (K < 1 || K > 65535) return fail(ISMPC_E_INVALID, "a multi-plan handle holds 1 .. 65535 parameter sets");
+        if (rows < 2) return fail(ISMPC_E_INVALID, "footstep plan needs at least 2 rows");
+        if ((long long)K * P > (1ll << 24)) return fail(ISMPC_E_ALLOC, "more (set, plan) pairs than one handle holds (2^24: each pair has its own anticipative tails)");
+        for (int p = 1; p < P; ++p)
+            for (int i = 0; i < rows; ++i)
+                if (std::memcmp(&ftsp[((size_t)p * rows + i) * 4 + 2], &ftsp[(size_t)i * 4 + 2], sizeof(double)) != 0)
+                    return fail(ISMPC_E_UNSUPPORTED, "multi-plan handle: plan " + std::to_string(p) + " differs from plan 0 in the z column (row " + std::to_string(i) +
+                                                     "); the plans of one handle share one height profile");
+        if (const char* pth = std::getenv("ISMPC_PATH"))
+            if (std::strcmp(pth, "dense") == 0) return fail(ISMPC_E_UNSUPPORTED, "multi-plan handle: ISMPC_PATH=dense reads one plan");
+    }
     if (sweep) {
         // the sets of a sweep share what fixes the shape of the problem; everything else may differ from set to set
         if (K < 1 || K > 65535) return fail(ISMPC_E_INVALID, "a sweep holds 1 .. 65535 parameter sets");
@@ -456,6 +503,58 @@ static int create_impl(const ismpc_params* params, int K, bool sweep, const doub
     if (const char* hm = std::getenv("ISMPC_HOST_MODE")) h->host_mode = std::atoi(hm) & 3;
     if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess ||
         hipEventCreate(&h->ev1) != hipSuccess) { ismpc_destroy(h); return fail(ISMPC_E_NO_DEVICE, "stream/event creation failed"); }
+    // multi-plan handle, part 1: every plan's tables side by side on the device -- midx, midy, midxy (the lane-group kernels' window),
+    // the step timings and, with ONE parameter set, the host-built tails (with several the tails are built on the device per pair, below)
+    const double *pl_midx = nullptr, *pl_midy = nullptr, *pl_midxy = nullptr, *pl_t = nullptr, *pl_tailx = nullptr, *pl_taily = nullptr;
+    if (P) {
+        const size_t nm = (size_t)t.nmid;
+        std::vector<double> mxy(2 * nm * P), tt((size_t)rows * P), tx(sweep ? 0 : nm * P), ty(sweep ? 0 : nm * P);
+        h->pl_midx.resize(nm * P); h->pl_midy.resize(nm * P);
+        for (int p = 0; p < P; ++p) {
+            ismpc::PlanTables pt;
+            ismpc::build_plan_tables(params[0], ftsp + (size_t)p * rows * 4, rows, pt);
+            std::copy(pt.midx.begin(), pt.midx.end(), h->pl_midx.begin() + p * nm); std::copy(pt.midy.begin(), pt.midy.end(), h->pl_midy.begin() + p * nm);
+            for (size_t n = 0; n < nm; ++n) { mxy[2 * (p * nm + n)] = pt.midx[n]; mxy[2 * (p * nm + n) + 1] = pt.midy[n]; }
+            std::copy(pt.ftsp_t.begin(), pt.ftsp_t.end(), tt.begin() + (size_t)p * rows);
+            if (!sweep) { std::copy(pt.tailx.begin(), pt.tailx.end(), tx.begin() + p * nm); std::copy(pt.taily.begin(), pt.taily.end(), ty.begin() + p * nm); }
+        }
+        rc = upload(h, h->pl_midx, &pl_midx);
+        if (rc == ISMPC_OK) rc = upload(h, h->pl_midy, &pl_midy);
+        if (rc == ISMPC_OK) rc = upload(h, mxy, &pl_midxy);
+        if (rc == ISMPC_OK) rc = upload(h, tt, &pl_t);
+        if (rc == ISMPC_OK && !sweep) rc = upload(h, tx, &pl_tailx);
+        if (rc == ISMPC_OK && !sweep) rc = upload(h, ty, &pl_taily);
+        if (rc != ISMPC_OK) { ismpc_destroy(h); return rc; }
+    }
+    // ... part 2: one record per (set, plan) pair, set-major -- the set's record (`base`) with the plan's tables in place of plan 0's
+    auto upload_pairs = [&](const std::vector<DevConst>& base, const DevConst** dst) -> int {
+        const size_t nm = (size_t)t.nmid;
+        std::vector<DevConst> pr(base.size() * (size_t)P);
+        for (size_t k = 0; k < base.size(); ++k)
+            for (int p = 0; p < P; ++p) {
+                DevConst& d = pr[k * P + p]; d = base[k];
+                d.midx = pl_midx + p * nm; d.midy = pl_midy + p * nm; d.midxy = pl_midxy + 2 * p * nm; d.ftsp_t = pl_t + (size_t)p * rows;
+                if (sweep) { d.tailx = h->sw.tailx + (k * P + p) * h->sw.s_tail; d.taily = h->sw.taily + (k * P + p) * h->sw.s_tail; }
+                else { d.tailx = pl_tailx + p * nm; d.taily = pl_taily + p * nm; }
+                d.sets = nullptr; d.nsets = 0; d.nplans = 0; d.order = nullptr;
+            }
+        void* sp = nullptr;
+        if (hipMalloc(&sp, sizeof(DevConst) * pr.size()) != hipSuccess) { (void)hipGetLastError(); return fail(ISMPC_E_ALLOC, "multi-plan handle: pair records allocation failed"); }
+        h->dev_allocs.push_back(sp);
+        if (hipMemcpy(sp, pr.data(), sizeof(DevConst) * pr.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(ISMPC_E_NO_DEVICE, "multi-plan handle: pair records upload failed");
+        *dst = static_cast<const DevConst*>(sp);
+        return ISMPC_OK;
+    };
+    if (P && !sweep) {
+        // one parameter set: the pair records are the handle's own constants per plan, once per lane layout it may launch with
+        const DevConst* recs = nullptr;
+        std::vector<DevConst> base(1, h->c);
+        rc = upload_pairs(base, &recs);
+        if (rc == ISMPC_OK && h->vqT32) { base[0].vqT = h->vqT32; rc = upload_pairs(base, &h->sets32); }
+        if (rc == ISMPC_OK && h->vqT8) { base[0].vqT = h->vqT8; rc = upload_pairs(base, &h->sets8); }
+        if (rc != ISMPC_OK) { ismpc_destroy(h); return rc; }
+        h->c.sets = recs; h->c.nsets = 1; h->c.nplans = P; h->nplans = P;
+    }
     if (sweep) {
         // every set's tables, built on the device (MFMA Newton-Schulz inverse of the K vertical Hessians, csrc/ismpc_sweep.hip), and one
         // DevConst record per set: the handle's, with the set's scalars and table pointers in place of set 0's host-built ones
@@ -466,7 +565,8 @@ static int create_impl(const ismpc_params* params, int K, bool sweep, const doub
         // against 9.17-9.26e8), so it is the default now
         const char* lp8 = std::getenv("ISMPC_LPI");
         const bool lanes8 = !(lp8 && std::atoi(lp8) == 16);
-        rc = ismpc::sweep_build(params, K, h->t, c.midx, c.midy, c.midz, c.e_lo, c.ne, 16, quad_R(t.p.N, 16), lanes8 ? 8 : 0, quad_R(t.p.N, 8), h->own_stream, h->sw, h->dev_allocs, serr);
+        rc = ismpc::sweep_build(params, K, h->t, P ? pl_midx : c.midx, P ? pl_midy : c.midy, c.midz, c.e_lo, c.ne, 16, quad_R(t.p.N, 16), lanes8 ? 8 : 0, quad_R(t.p.N, 8), h->own_stream, h->sw, h->dev_allocs, serr,
+                                P ? P : 1);
         if (rc != ISMPC_OK) { ismpc_destroy(h); return fail(rc, serr); }
         std::vector<DevConst> cs((size_t)K, h->c);
         for (int k = 0; k < K; ++k) {
@@ -479,9 +579,20 @@ static int create_impl(const ismpc_params* params, int K, bool sweep, const doub
             d.Wt = h->sw.Wt + (size_t)k * h->sw.s_W; d.SW = h->sw.SW + (size_t)k * h->sw.s_W;
             d.HSt = h->sw.HSt + (size_t)k * h->sw.s_HS; d.SHSt = h->sw.SHSt + (size_t)k * h->sw.s_HS;
             if (h->sw.dU) { d.dU = h->sw.dU + (size_t)k * h->sw.s_dU; d.SdU = h->sw.SdU + (size_t)k * h->sw.s_dU; }      // (plans with mid_z != 0)
-            d.tailx = h->sw.tailx + (size_t)k * h->sw.s_tail; d.taily = h->sw.taily + (size_t)k * h->sw.s_tail;
+            d.tailx = h->sw.tailx + (size_t)k * (P ? P : 1) * h->sw.s_tail; d.taily = h->sw.taily + (size_t)k * (P ? P : 1) * h->sw.s_tail;
             d.Hinv = nullptr; d.W = nullptr; d.vq = nullptr; d.sets = nullptr; d.nsets = 0;
         }
+        if (P) {
+            // several sets x several plans: the pair records over the sets' device-built records (16 lanes and, beside them, 8)
+            const DevConst* recs = nullptr;
+            rc = upload_pairs(cs, &recs);
+            if (rc == ISMPC_OK && h->sw.vqT2) {
+                for (int k = 0; k < K; ++k) cs[k].vqT = h->sw.vqT2 + (size_t)k * h->sw.s_vqT2;
+                rc = upload_pairs(cs, &h->sets8);
+            }
+            if (rc != ISMPC_OK) { ismpc_destroy(h); return rc; }
+            h->c.sets = recs; h->c.nsets = K; h->c.nplans = P; h->nplans = P;
+        } else {
         void* sp = nullptr;
         if (hipMalloc(&sp, sizeof(DevConst) * (size_t)K) != hipSuccess) { ismpc_destroy(h); return fail(ISMPC_E_ALLOC, "sweep: set records allocation failed"); }
         h->dev_allocs.push_back(sp);
@@ -494,6 +605,7 @@ static int create_impl(const ismpc_params* params, int K, bool sweep, const doub
             h->dev_allocs.push_back(sp8);
             if (hipMemcpy(sp8, cs.data(), sizeof(DevConst) * (size_t)K, hipMemcpyHostToDevice) != hipSuccess) { ismpc_destroy(h); return fail(ISMPC_E_NO_DEVICE, "sweep: set records upload failed"); }
             h->sets8 = static_cast<const DevConst*>(sp8);
+        }
         }
     }
     {
@@ -516,14 +628,36 @@ int ismpc_create_sweep(const ismpc_params* params, int n_sets, const double* fts
     return create_impl(params, n_sets, true, ftsp, rows, device, out);
 }
 
+int ismpc_create_plans(const ismpc_params* params, int n_sets, const double* ftsp, int n_plans, int rows, int device, ismpc_handle** out)
+{
+    if (n_plans < 1) return fail(ISMPC_E_INVALID, "a multi-plan handle holds 1 .. 32767 footstep plans");
+    return create_impl(params, n_sets, n_sets > 1, ftsp, rows, device, out, n_plans);
+}
+
+int ismpc_plans_info(const ismpc_handle* h, int* n_plans)
+{
+    if (!h || !n_plans) return fail(ISMPC_E_INVALID, "null argument");
+    *n_plans = h->nplans ? h->nplans : 1;
+    return ISMPC_OK;
+}
+
+int ismpc_get_midpoint_plan(const ismpc_handle* h, int plan, double* dst, int capacity_rows)
+{
+    if (!h || !dst || capacity_rows < h->t.nmid || plan < 0 || plan >= (h->nplans ? h->nplans : 1)) return fail(ISMPC_E_INVALID, "bad argument");
+    if (!h->nplans) return ismpc_get_midpoint(h, dst, capacity_rows);
+    const size_t o = (size_t)plan * h->t.nmid;
+    for (int i = 0; i < h->t.nmid; ++i) { dst[3*i] = h->pl_midx[o + i]; dst[3*i+1] = h->pl_midy[o + i]; dst[3*i+2] = h->t.midz[i]; }
+    return ISMPC_OK;
+}
+
 int ismpc_sweep_bind(ismpc_handle* h, int batch, const ismpc_tick_in* in_dev, void* stream)
 {
     if (!h || batch < 0 || (batch > 0 && !in_dev)) return fail(ISMPC_E_INVALID, "bad argument");
-    if (!h->sweep) return fail(ISMPC_E_INVALID, "ismpc_sweep_bind needs a handle of ismpc_create_sweep");
+    if (!h->sweep && !h->nplans) return fail(ISMPC_E_INVALID, "ismpc_sweep_bind needs a handle of ismpc_create_sweep or ismpc_create_plans");
     ON_DEVICE(h);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (batch == 0) { h->order_batch = 0; return ISMPC_OK; }
-    const int nb = h->c.nsets + 1;
+    const int nb = h->c.nsets * (h->nplans ? h->nplans : 1) + 1;      // (a multi-plan handle sorts by (set, plan) pair)
     if (batch + nb > h->order_cap) {
         HIP_TRY(hipDeviceSynchronize());                       // (a set-up call: launches that still read the old order finish first)
         h->order_batch = 0;
@@ -532,9 +666,11 @@ int ismpc_sweep_bind(ismpc_handle* h, int batch, const ismpc_tick_in* in_dev, vo
     int* cursor = h->order + batch;
     HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(int) * (size_t)nb, s));
     const dim3 grid((batch + 255) / 256), block(256);
-    hipLaunchKernelGGL(sweep_sort_hist, grid, block, 0, s, in_dev, batch, h->c.nsets, cursor);
+    if (h->nplans) hipLaunchKernelGGL(plans_sort_hist, grid, block, 0, s, h->c, in_dev, batch, cursor);
+    else           hipLaunchKernelGGL(sweep_sort_hist, grid, block, 0, s, in_dev, batch, h->c.nsets, cursor);
     hipLaunchKernelGGL(sweep_sort_scan, dim3(1), block, 0, s, cursor, nb);
-    hipLaunchKernelGGL(sweep_sort_scatter, grid, block, 0, s, in_dev, batch, h->c.nsets, cursor, h->order);
+    if (h->nplans) hipLaunchKernelGGL(plans_sort_scatter, grid, block, 0, s, h->c, in_dev, batch, cursor, h->order);
+    else           hipLaunchKernelGGL(sweep_sort_scatter, grid, block, 0, s, in_dev, batch, h->c.nsets, cursor, h->order);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     h->order_batch = batch;
@@ -579,7 +715,8 @@ int ismpc_sweep_verify_tables(ismpc_handle* h, int set, double* rel_err)
     rel_err[4] = rel(d, t.HSt);
     if (!fetch(S.SHSt + (size_t)set * S.s_HS, S.s_HS, d)) return fail(ISMPC_E_NO_DEVICE, "download failed");
     rel_err[5] = rel(d, t.SHSt);
-    { std::vector<double> dx, dy; if (!fetch(S.tailx + (size_t)set * S.s_tail, S.s_tail, dx) || !fetch(S.taily + (size_t)set * S.s_tail, S.s_tail, dy)) return fail(ISMPC_E_NO_DEVICE, "download failed");
+    { std::vector<double> dx, dy; const size_t ts = (size_t)set * (h->nplans ? h->nplans : 1) * S.s_tail;      // (a multi-plan handle: the tails of (set, plan 0))
+      if (!fetch(S.tailx + ts, S.s_tail, dx) || !fetch(S.taily + ts, S.s_tail, dy)) return fail(ISMPC_E_NO_DEVICE, "download failed");
       rel_err[6] = std::max(rel(dx, t.tailx), rel(dy, t.taily)); }
     rel_err[7] = 0.0;
     for (int pass = 0; pass < (S.vqT2 ? 2 : 1); ++pass) {   // the lane-group layouts (16 lanes, 8 lanes), against the host's re-striding of ITS vtab
@@ -728,15 +865,21 @@ int ismpc_rollout_device(ismpc_handle* h, int batch, ismpc_tick_in* state_dev, i
             hipLaunchKernelGGL(resume, rgrid, qblock, 0, s, cq, state_dev, traj_dev, batch, first_frame, ticks, h->zstop, lid);
         };
         auto note = [&](int lanes, int r, int rw) {          // (ismpc_last_launch_info: the rollout and its resume launch)
-            const int v[8] = {ISMPC_KERNEL_ROLLOUT_QUAD, lanes, r, rw, h->sweep ? 1 : 0, 2, batch, 0};
+            const int v[8] = {ISMPC_KERNEL_ROLLOUT_QUAD, lanes, r, rw, (h->sweep ? 1 : 0) | (h->nplans ? 2 : 0), 2, batch, 0};
             std::memcpy(h->last_launch, v, sizeof(v));
         };
         // (a sweep handle rolls out at 16 lanes per instance: the SW kernels are instantiated for that shape only)
         if (h->sweep && lpi != 16) return fail(ISMPC_E_UNSUPPORTED, "parameter sweep: rollouts take 16 lanes per instance");
-        if (h->sweep)
+        if (h->nplans) {
+            cq.sets = (lpi == 8 && h->sets8) ? h->sets8 : ((lpi == 32 && h->sets32) ? h->sets32 : h->c.sets);
+            quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
+                roll(ismpc_rollout_quad<RR, LL, RW_, false, 2>, ismpc_rollout_quad<RR, LL, RW_, true, 2>);
+                note(LL, RR, RW_);
+            });
+        } else if (h->sweep)
             quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
                 if constexpr (LL == 16) {
-                    roll(ismpc_rollout_quad<RR, 16, RW_, false, true>, ismpc_rollout_quad<RR, 16, RW_, true, true>);
+                    roll(ismpc_rollout_quad<RR, 16, RW_, false, 1>, ismpc_rollout_quad<RR, 16, RW_, true, 1>);
                     note(16, RR, RW_);
                 }
             });

@@ -324,12 +324,14 @@ __global__ __launch_bounds__(256) void sweep_layout(const double* __restrict__ v
     }
 }
 
-// ---- anticipative tails (MPCSolver.cpp:183-184, 381-383) for this set's eta = sqrt(g / h_des)
+// ---- anticipative tails (MPCSolver.cpp:183-184, 381-383) for this set's eta = sqrt(g / h_des); grid.z = the plans of a multi-plan
+// handle (midx / midy: one run of nmid per plan; the tails of (set, plan) at slot set * plans + plan), 1 otherwise
 __global__ __launch_bounds__(256) void sweep_tail(const double* __restrict__ par, const double* __restrict__ midx, const double* __restrict__ midy, int nmid,
                                                   double* __restrict__ tailx, double* __restrict__ taily, size_t s_tail, int N, double dt)
 {
     __shared__ double wgt[256];
-    const int set = blockIdx.y;
+    const int set = blockIdx.y, plan = blockIdx.z;
+    midx += (size_t)plan * nmid; midy += (size_t)plan * nmid;
     const double eta = par[set * PAR + 5];
     if ((int)threadIdx.x < N) wgt[threadIdx.x] = eta * dt * exp(-dt * eta * (double)threadIdx.x);
     __syncthreads();
@@ -338,7 +340,8 @@ __global__ __launch_bounds__(256) void sweep_tail(const double* __restrict__ par
     double sx = 0.0, sy = 0.0;
     if (idx + 2 * N <= nmid)
         for (int i = 0; i < N; ++i) { sx += wgt[i] * midx[idx + N + i]; sy += wgt[i] * midy[idx + N + i]; }
-    tailx[(size_t)set * s_tail + idx] = sx; taily[(size_t)set * s_tail + idx] = sy;
+    const size_t slot = (size_t)set * gridDim.z + plan;
+    tailx[slot * s_tail + idx] = sx; taily[slot * s_tail + idx] = sy;
 }
 
 // ---- did the build work?  Per set: max |I - H X| over the N x N block (a Hessian that is not positive definite, or one so badly
@@ -378,7 +381,7 @@ int dalloc(double** p, size_t n, std::vector<void*>& allocs, std::string& err)
 }  // namespace
 
 int sweep_build(const ismpc_params* sets, int K, const Tables& t0, const double* midx_dev, const double* midy_dev, const double* midz_dev, const int* e_lo_dev,
-                const int* ne_dev, int lpi, int R, int lpi2, int R2, hipStream_t s, SweepSlabs& o, std::vector<void*>& allocs, std::string& err)
+                const int* ne_dev, int lpi, int R, int lpi2, int R2, hipStream_t s, SweepSlabs& o, std::vector<void*>& allocs, std::string& err, int n_plans)
 {
     const int N = t0.p.N;
     if (K < 1) { err = "a sweep needs at least one parameter set"; return ISMPC_E_INVALID; }
@@ -414,8 +417,8 @@ int sweep_build(const ismpc_params* sets, int K, const Tables& t0, const double*
         (rc = dalloc(&o.vqT, (size_t)K * o.s_vqT, allocs, err)) || (lpi2 > 0 && (rc = dalloc(&o.vqT2, (size_t)K * o.s_vqT2, allocs, err))) ||
         (rc = dalloc(&o.Wt, (size_t)K * o.s_W, allocs, err)) ||
         (rc = dalloc(&o.SW, (size_t)K * o.s_W, allocs, err)) || (rc = dalloc(&o.HSt, (size_t)K * o.s_HS, allocs, err)) ||
-        (rc = dalloc(&o.SHSt, (size_t)K * o.s_HS, allocs, err)) || (rc = dalloc(&o.tailx, (size_t)K * o.s_tail, allocs, err)) ||
-        (rc = dalloc(&o.taily, (size_t)K * o.s_tail, allocs, err))) return rc;
+        (rc = dalloc(&o.SHSt, (size_t)K * o.s_HS, allocs, err)) || (rc = dalloc(&o.tailx, (size_t)K * n_plans * o.s_tail, allocs, err)) ||
+        (rc = dalloc(&o.taily, (size_t)K * n_plans * o.s_tail, allocs, err))) return rc;
     SW_TRY(hipMemsetAsync(o.vtab, 0, (size_t)K * o.s_vtab * sizeof(double), s));
     SW_TRY(hipMemsetAsync(o.Wt, 0, (size_t)K * o.s_W * sizeof(double), s));
     SW_TRY(hipMemsetAsync(o.SW, 0, (size_t)K * o.s_W * sizeof(double), s));
@@ -460,7 +463,7 @@ int sweep_build(const ismpc_params* sets, int K, const Tables& t0, const double*
                        e_lo_dev, ne_dev, t0.npat, t0.Fmax, o.vtab, o.s_vtab, o.Wt, o.SW, o.s_W, N, NG, dt);
     hipLaunchKernelGGL(sweep_layout, dim3(t0.npat + 1, K), dim3(256), 0, s, (const double*)o.vtab, o.s_vtab, o.vqT, o.s_vqT, lpi, R);
     if (lpi2 > 0) hipLaunchKernelGGL(sweep_layout, dim3(t0.npat + 1, K), dim3(256), 0, s, (const double*)o.vtab, o.s_vtab, o.vqT2, o.s_vqT2, lpi2, R2);
-    hipLaunchKernelGGL(sweep_tail, dim3((t0.nmid + 255) / 256, K), dim3(256), 0, s, (const double*)o.par, midx_dev, midy_dev, t0.nmid, o.tailx, o.taily, o.s_tail, N, dt);
+    hipLaunchKernelGGL(sweep_tail, dim3((t0.nmid + 255) / 256, K, n_plans), dim3(256), 0, s, (const double*)o.par, midx_dev, midy_dev, t0.nmid, o.tailx, o.taily, o.s_tail, N, dt);
     SW_TRY(hipGetLastError());
     SW_TRY(hipEventRecord(e1, s));
     // the build is checked, not trusted: |I - H X| of every set and finite tables

@@ -40,8 +40,9 @@ struct SweepSlabs {                 // one device slab per table kind, set k at 
 // (a plan with mid_z != 0 adds the per-frame offsets dU, SdU of every set: sweep_du)
 // Builds every per-set table on `stream` (synchronises before returning).  `t0` = host tables of set 0 (plan, patterns, structure).
 // lpi / R: lane-group layout of vqT (ismpc_hip.hip quad_R); lpi2 / R2: a second layout beside it (vqT2; lpi2 = 0: none).  All device
-// memory is appended to `allocs`.
+// memory is appended to `allocs`.  n_plans > 1 (ismpc_create_plans): midx_dev / midy_dev hold one run of nmid per plan (mid_z is common to
+// the plans) and the tails are built for every (set, plan) pair, at slab + (set * n_plans + plan) * s_tail.
 int sweep_build(const ismpc_params* sets, int K, const Tables& t0, const double* midx_dev, const double* midy_dev, const double* midz_dev, const int* e_lo_dev,
-                const int* ne_dev, int lpi, int R, int lpi2, int R2, hipStream_t stream, SweepSlabs& out, std::vector<void*>& allocs, std::string& err);
+                const int* ne_dev, int lpi, int R, int lpi2, int R2, hipStream_t stream, SweepSlabs& out, std::vector<void*>& allocs, std::string& err, int n_plans = 1);
 
 }  // namespace ismpc

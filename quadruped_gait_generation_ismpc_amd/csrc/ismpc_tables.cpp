@@ -50,6 +50,36 @@ static void chol_inverse(const std::vector<ld>& L, int n, std::vector<ld>& inv)
         }
 }
 
+void build_plan_tables(const ismpc_params& p, const double* ftsp, int rows, PlanTables& t)
+{
+    const int N = p.N, S = p.S, F = p.F, nmid = rows * (S + F);
+    const double eta = std::sqrt(p.g / p.h_des);
+    // ---- ftsp_midpoint, MPCSolver.cpp:167-180 (same operation order as the reference)
+    t.midx.assign(nmid, 0.0); t.midy.assign(nmid, 0.0); t.midz.assign(nmid, 0.0);
+    std::vector<double>* col[3] = { &t.midx, &t.midy, &t.midz };
+    for (int i = 0; i < rows - 1; ++i)
+        for (int c = 0; c < 3; ++c) {
+            const double a = ftsp[i*4+c], b = ftsp[(i+1)*4+c];
+            for (int r = 0; r < S; ++r) (*col[c])[i*(S+F)+r] = a * 1.0;
+            for (int r = 0; r < F; ++r) (*col[c])[i*(S+F)+S+r] = a * 1.0 + (b - a) * ((double)r / (double)F);
+        }
+    t.ftsp_t.resize(rows);
+    for (int i = 0; i < rows; ++i) t.ftsp_t[i] = ftsp[i*4+3];
+
+    // ---- anticipative tail, MPCSolver.cpp:183-184 and :381-383: depends on idx only
+    std::vector<double> deltas(N);
+    for (int i = 0; i < N; ++i) deltas[i] = std::exp(-p.mpc_dt * eta * i);
+    t.tailx.assign(nmid, 0.0); t.taily.assign(nmid, 0.0);
+    for (int idx = 0; idx + 2*N <= nmid; ++idx) {
+        double sx = 0, sy = 0;
+        for (int i = 0; i < N; ++i) {
+            const double wgt = eta * p.mpc_dt * deltas[i];
+            sx += wgt * t.midx[idx+N+i]; sy += wgt * t.midy[idx+N+i];
+        }
+        t.tailx[idx] = sx; t.taily[idx] = sy;
+    }
+}
+
 int build_tables(const ismpc_params& p, const double* ftsp, int rows, Tables& t, std::string& err)
 {
     if (!ftsp || rows < 2) { err = "footstep plan needs at least 2 rows"; return ISMPC_E_INVALID; }
@@ -120,29 +150,12 @@ int build_tables(const ismpc_params& p, const double* ftsp, int rows, Tables& t,
             }
     }
 
-    // ---- ftsp_midpoint, MPCSolver.cpp:167-180 (same operation order as the reference)
-    t.midx.assign(t.nmid, 0.0); t.midy.assign(t.nmid, 0.0); t.midz.assign(t.nmid, 0.0);
-    std::vector<double>* col[3] = { &t.midx, &t.midy, &t.midz };
-    for (int i = 0; i < rows - 1; ++i)
-        for (int c = 0; c < 3; ++c) {
-            const double a = ftsp[i*4+c], b = ftsp[(i+1)*4+c];
-            for (int r = 0; r < S; ++r) (*col[c])[i*(S+F)+r] = a * 1.0;
-            for (int r = 0; r < F; ++r) (*col[c])[i*(S+F)+S+r] = a * 1.0 + (b - a) * ((double)r / (double)F);
-        }
-    t.ftsp_t.resize(rows);
-    for (int i = 0; i < rows; ++i) t.ftsp_t[i] = ftsp[i*4+3];
-
-    // ---- anticipative tail, MPCSolver.cpp:183-184 and :381-383: depends on idx only
-    std::vector<double> deltas(N);
-    for (int i = 0; i < N; ++i) deltas[i] = std::exp(-p.mpc_dt * t.eta * i);
-    t.tailx.assign(t.nmid, 0.0); t.taily.assign(t.nmid, 0.0);
-    for (int idx = 0; idx + 2*N <= t.nmid; ++idx) {
-        double sx = 0, sy = 0;
-        for (int i = 0; i < N; ++i) {
-            const double wgt = t.eta * p.mpc_dt * deltas[i];
-            sx += wgt * t.midx[idx+N+i]; sy += wgt * t.midy[idx+N+i];
-        }
-        t.tailx[idx] = sx; t.taily[idx] = sy;
+    // ---- what the plan alone decides: ftsp_midpoint, the step timings, the anticipative tails
+    {
+        PlanTables pt;
+        build_plan_tables(p, ftsp, rows, pt);
+        t.midx.swap(pt.midx); t.midy.swap(pt.midy); t.midz.swap(pt.midz);
+        t.tailx.swap(pt.tailx); t.taily.swap(pt.taily); t.ftsp_t.swap(pt.ftsp_t);
     }
 
     // ---- affine tables of the vertical stage (see ismpc_tables.hpp) ----

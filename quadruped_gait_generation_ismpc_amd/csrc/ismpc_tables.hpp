@@ -45,6 +45,11 @@ struct Tables {
     std::vector<double> HSt, SHSt;          // N x NT each
 };
 
+// What a footstep plan alone decides (with eta = sqrt(g / h_des) for the tails): build_tables() fills its own members through this,
+// and a multi-plan handle (ismpc_create_plans) builds one per plan.  `p` and `rows` as build_tables() has checked them.
+struct PlanTables { std::vector<double> midx, midy, midz, tailx, taily, ftsp_t; };
+void build_plan_tables(const ismpc_params& p, const double* ftsp, int rows, PlanTables& out);
+
 // Returns ISMPC_OK or an ISMPC_E_* code; on error `err` explains.
 int build_tables(const ismpc_params& p, const double* ftsp, int rows, Tables& out, std::string& err);
 

@@ -22,6 +22,13 @@ ST_ERROR_MASK = ST_X_INFEASIBLE | ST_Y_INFEASIBLE | ST_BAD_INDEX | ST_Z_FAILED
 KERNEL_FAMILIES = ("none", "quad", "quad_inline", "quad_one", "rollout_quad", "affine", "dense")
 
 
+def pack_reserved(set, plan):
+    """ISMPC_RESERVED(set, plan) of include/ismpc.h, over scalars or numpy arrays: what ismpc_tick_in.reserved holds on a
+    multi-plan handle -- low 16 bits the parameter set, the bits above the plan."""
+    v = (np.asarray(plan, dtype=np.int64) << 16) | (np.asarray(set, dtype=np.int64) & 0xFFFF)
+    return v.astype(np.int32) if v.ndim else int(np.int32(v))
+
+
 class IsmpcError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"ismpc error {code}: {msg}")
@@ -115,6 +122,34 @@ class MPCSolver:
         self.itr = 0; self.fsCount = 0; self.old_fsCount = 0; self.ct = 0; self.xz_dot = 0.0; self.yz_dot = 0.0
         return self
 
+    @classmethod
+    def plans(cls, ftsp_list, params=None, device=0):
+        """Multi-plan handle (ismpc_create_plans): one handle for `len(ftsp_list)` footstep plans of equal shape and one parameter
+        set (`params`: None or an ismpc_params) or several (a list); instance i runs with tick_in["reserved"][i] =
+        pack_reserved(set, plan)."""
+        self = cls.__new__(cls)
+        self._lib = _lib.load()
+        self.params_list = list(params) if isinstance(params, (list, tuple)) else [params if params is not None else default_params()]
+        self.params = self.params_list[0] if self.params_list else None
+        self.ftsp = np.ascontiguousarray(np.stack([np.asarray(f, dtype=np.float64) for f in ftsp_list]) if len(ftsp_list) else np.zeros((0, 2, 4)))
+        if self.ftsp.ndim != 3 or self.ftsp.shape[2] != 4:
+            raise ValueError("every plan must be rows x 4, all of one shape")
+        arr = (Params * max(len(self.params_list), 1))(*self.params_list)
+        h = C.c_void_p()
+        rc = self._lib.ismpc_create_plans(C.cast(arr, C.c_void_p), len(self.params_list), self.ftsp.ctypes.data_as(C.c_void_p),
+                                          self.ftsp.shape[0], self.ftsp.shape[1], int(device), C.byref(h))
+        if rc != 0:
+            raise IsmpcError(rc, _lib.last_error())
+        self._h = h; self.device = int(device)
+        self.itr = 0; self.fsCount = 0; self.old_fsCount = 0; self.ct = 0; self.xz_dot = 0.0; self.yz_dot = 0.0
+        return self
+
+    def plans_info(self):
+        """ismpc_plans_info: the number of footstep plans the handle holds (1 unless it came from MPCSolver.plans)."""
+        n = C.c_int()
+        self._check(self._lib.ismpc_plans_info(self._h, C.byref(n)))
+        return {"n_plans": n.value}
+
     def sweep_info(self):
         n, it, gl, ms = C.c_int(), C.c_int(), C.c_int(), C.c_double()
         self._check(self._lib.ismpc_sweep_info(self._h, C.byref(n), C.byref(it), C.byref(gl), C.byref(ms)))
@@ -204,12 +239,16 @@ class MPCSolver:
 
     def launch_info(self):
         """ismpc_last_launch_info: which kernel the most recent step or rollout of this handle enqueued, as recorded by the host at the
-        launch.  family is one of KERNEL_FAMILIES; lanes, R, RW are the instantiated shape; kernels is 1 or 2 launches per step."""
+        launch.  family is one of KERNEL_FAMILIES; lanes, R, RW are the instantiated shape; kernels is 1 or 2 launches per step.
+        "plans": True is there when the multi-plan instantiation ran (bit 1 of out8[4]); a plain or sweep handle's dict is what it always was."""
         a = np.zeros(8, dtype=np.int32)
         self._check(self._lib.ismpc_last_launch_info(self._h, a.ctypes.data_as(C.c_void_p)))
         v = [int(x) for x in a]
-        return {"family": KERNEL_FAMILIES[v[0]], "lanes": v[1], "R": v[2], "RW": v[3], "sweep": bool(v[4]), "kernels": v[5],
+        info = {"family": KERNEL_FAMILIES[v[0]], "lanes": v[1], "R": v[2], "RW": v[3], "sweep": bool(v[4] & 1), "kernels": v[5],
                 "batch": v[6], "bound_order": bool(v[7])}
+        if v[4] & 2:
+            info["plans"] = True
+        return info
 
     def set_timing(self, enabled=True):
         self._check(self._lib.ismpc_set_timing(self._h, 1 if enabled else 0))
@@ -217,10 +256,10 @@ class MPCSolver:
     def last_kernel_ms(self):
         return float(self._lib.ismpc_last_kernel_ms(self._h))
 
-    def midpoint(self):
+    def midpoint(self, plan=0):
         n = self._lib.ismpc_midpoint_rows(self._h)
         m = np.zeros((n, 3))
-        self._check(self._lib.ismpc_get_midpoint(self._h, m.ctypes.data_as(C.c_void_p), n))
+        self._check(self._lib.ismpc_get_midpoint_plan(self._h, int(plan), m.ctypes.data_as(C.c_void_p), n))
         return m
 
     # ---- torch conveniences (device memory and streams are torch's; the compute is not) ----

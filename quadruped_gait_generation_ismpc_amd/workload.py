@@ -92,6 +92,29 @@ def make_inst_mc(batch, seed=SEED, stream=0, C=200):
     return inst, np.ascontiguousarray(push)
 
 
+def make_plans(P, params=None, seed=SEED):
+    """P footstep plans for a multi-plan Formulation B handle (ismpc_create_plans), rows x 4 each, of the shape of reference_plan():
+    plan 0 IS the reference's plan (Controller.cpp:89-97); every other plan draws its stride L ~ U(0.12, 0.28) m, half stance width
+    w ~ U(0.06, 0.10) m, heading theta ~ U(-1, 1) rad (the rows rotated about the origin) and step time T in {40, 45, 50} frames, at z = 0.
+    Counter based: plan p depends on (seed, p) only."""
+    from .solver import default_params, reference_plan
+    p0 = params if params is not None else default_params()
+    out = [reference_plan(params=p0)]
+    rows = out[0].shape[0]
+    i = np.arange(1, rows)
+    for p in range(1, P):
+        u = np.random.Generator(np.random.Philox(key=seed + 104729, counter=[0, 0, 0, p])).random(4)
+        L, w, th = 0.12 + 0.16 * u[0], 0.06 + 0.04 * u[1], -1.0 + 2.0 * u[2]
+        T = (40, 45, 50)[min(int(u[3] * 3), 2)]
+        x, y = (i - 1) * L, (-1.0) ** (i - 1) * w
+        f = np.zeros((rows, 4))
+        f[1:, 0] = np.cos(th) * x - np.sin(th) * y
+        f[1:, 1] = np.sin(th) * x + np.cos(th) * y
+        f[1:, 3] = (p0.mpc_dt / p0.control_dt) * T * i
+        out.append(f)
+    return out
+
+
 def make_sweep_params(K, N=100, seed=SEED):
     """K parameter sets for a Formulation B sweep (ismpc_create_sweep): set 0 = the reference's constants (parameters.cpp:9-45,
     MPCSolver.cpp:253-255); the others draw mass, CoM height, the three vertical-QP weights and the foot width around them."""
