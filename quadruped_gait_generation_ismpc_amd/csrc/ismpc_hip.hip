@@ -16,7 +16,10 @@
 //                         (:158-160; z_active_set), its launch ismpc_tick_affine_fallback and its callable forms fallback_call*
 //   ismpc_b_group.hpp     the DEFAULT for N <= 128: several instances per wavefront, one group of LPI lanes each
 //                         (ismpc_tick_quad, _inline, _one, ismpc_rollout_quad), and the sort of ismpc_sweep_bind
-//   this file             ismpc_handle and its run-time knobs, pick_layout() / quad_R() / launch(), the extern "C" entry points
+//   ismpc_tables.{hpp,cpp}  the host tables (long double) and lane_group_tables(), their re-striding for the lane-group kernels
+//   this file             ismpc_handle; the dispatch: quad_shape() / quad_R() (shape), pick_layout() / quad_launch() (lanes, constants, grid),
+//                         with_sw() (handle kind), launch(); the constructor in stages (read_knobs(), check_args(), upload_tables(),
+//                         upload_plans() / pair_records() / sweep_records() / upload_records(), create_impl()); the extern "C" entry points
 //
 // Which kernel a step of the default path takes (launch() below; ISMPC_LPI / ISMPC_ONE_LAUNCH override):
 //   lanes per instance   32 up to LPI32_BATCH = 2 048 instances, 16 up to LPI16_BATCH = 8 192, 8 beyond (closed loops keep 16)
@@ -35,6 +38,7 @@
 #include <string>
 #include <vector>
 #include <new>
+#include <memory>
 #include <algorithm>
 #include <type_traits>
 #include "ismpc_tables.hpp"
@@ -92,8 +96,9 @@ struct ismpc_handle {
     const DevConst* sets32 = nullptr;                                 // multi-plan handles that choose the layout per launch: the pair records with the 32-lane tables
     int nplans = 0;               // ismpc_create_plans: P footstep plans, c.sets = one record per (set, plan) pair; 0 for every other handle
     std::vector<double> pl_midx, pl_midy;                             // ... and the host copy of every plan's midpoint columns (P x nmid each)
+    int plans() const { return nplans ? nplans : 1; }
     bool kernel_rollout = true;   // closed loops run inside one launch (ismpc_rollout_quad); ISMPC_ROLLOUT=host: one launch per tick
-    DevConst* c_dev = nullptr;    // the constants in device memory (the one-launch kernel's fallback call reads them there)
+    const DevConst* c_dev = nullptr;   // the constants in device memory (the one-launch kernel's fallback call reads them there)
     bool sweep = false;           // ismpc_create_sweep: K parameter sets, tables built on the device (csrc/ismpc_sweep.hip)
     ismpc::SweepSlabs sw; std::vector<ismpc_params> sets; std::vector<double> ftsp;   // (the plan as given: ismpc_sweep_verify_tables rebuilds a set on the host)
     int* order = nullptr; int order_cap = 0, order_batch = 0;   // ismpc_sweep_bind: instances of the bound batch sorted by parameter set (+ nsets + 1 bucket cursors)
@@ -162,6 +167,40 @@ LaneLayout pick_layout(const ismpc_handle* h, int batch, bool per_tick)
     if ((h->lpi_auto || (h->sweep && h->sets8)) && h->vqT8 && per_tick && batch > LPI16_BATCH) return {8, h->vqT8, h->tzgT8};
     return {h->lpi, h->c.vqT, h->c.tzgT};
 }
+// What kind of handle it is, in the one place that says so.  The kernels take it as their SW template argument -- 2: a multi-plan handle
+// (each instance's (set, plan) pair through c.sets), 1: a parameter sweep (each instance's set through c.sets), 0: neither -- and
+// ismpc_last_launch_info as its form bits (bit 0 = sweep, bit 1 = multi-plan instantiation).  with_sw() calls f(SW) with the compile-time value and returns what f returns.
+int form_bits(const ismpc_handle* h) { return (h->sweep ? 1 : 0) | (h->nplans ? 2 : 0); }
+template <class F> auto with_sw(const ismpc_handle* h, F&& f)
+{
+    if (h->nplans) return f(std::integral_constant<int, 2>{});
+    if (h->sweep) return f(std::integral_constant<int, 1>{});
+    return f(std::integral_constant<int, 0>{});
+}
+// Which (lanes per instance, SW) pairs the lane-group kernels are instantiated for: SW = 0 and SW = 2 at every lane count; SW = 1 at 16 and
+// 8 lanes for the tick kernels and at 16 lanes only for the rollout (a sweep handle takes no other: create_impl() gives it 16, pick_layout() 8)
+constexpr bool has_tick_quad(int lpi, int sw) { return sw != 1 || lpi != 32; }
+constexpr bool has_rollout_quad(int lpi, int sw) { return sw != 1 || lpi == 16; }
+
+// What a launch of a lane-group kernel needs, for launch() and ismpc_rollout_device(): the lanes per instance of pick_layout(), the constants
+// with that layout's affine tables and set records, the order of ismpc_sweep_bind where it applies, and the grid.
+struct QuadLaunch { int lpi, waves; dim3 grid, block; DevConst c; };
+// (sweep and multi-plan handles: the records that go with the lane layout; a plain handle has none)
+const DevConst* sets_for(const ismpc_handle* h, int lpi)
+{
+    return (lpi == 8 && h->sets8) ? h->sets8 : ((lpi == 32 && h->sets32) ? h->sets32 : h->c.sets);
+}
+QuadLaunch quad_launch(const ismpc_handle* h, int batch, bool per_tick)
+{
+    const LaneLayout lay = pick_layout(h, batch, per_tick);
+    const int waves = (batch * lay.lpi + 63) / 64;
+    QuadLaunch q{lay.lpi, waves, dim3((waves + ISMPC_QUAD_WAVES - 1) / ISMPC_QUAD_WAVES), dim3(64 * ISMPC_QUAD_WAVES), h->c};
+    q.c.vqT = lay.vqT; q.c.tzgT = lay.tzgT;
+    q.c.sets = sets_for(h, lay.lpi);
+    // (ismpc_sweep_bind; per-tick launches of the bound batch only, and never a plain handle: ismpc_sweep_bind refuses it)
+    q.c.order = (h->order && h->order_batch == batch && per_tick && form_bits(h) != 0) ? h->order : nullptr;
+    return q;
+}
 // Page-locked AND device-mapped over its whole length: both ends of [p, p + bytes) are host allocations known to the runtime and the
 // device addresses of the two ends are `bytes - 1` apart (one mapping, or adjacent ones that continue each other).  A registration that
 // covers only the head of the buffer, or an interior pointer near the end of a pinned block, fails this and takes the staged path
@@ -188,8 +227,8 @@ int launch(ismpc_handle* h, int batch, const ismpc_tick_in* in, ismpc_tick_in* s
         hipLaunchKernelGGL(kernel, g, b, lds, s, c, in, state, out, u_traj, batch, rollout_frame, more...);
     };
     // what this step enqueues, for ismpc_last_launch_info: written where the kernel is launched, from the same shape values
-    auto note = [&](int family, int lanes, int r, int rw, int form, int kernels, bool ordered) {      // form: bit 0 = sweep, bit 1 = multi-plan instantiation
-        const int v[8] = {family, lanes, r, rw, form, kernels, batch, ordered ? 1 : 0};
+    auto note = [&](int family, int lanes, int r, int rw, int kernels, bool ordered) {
+        const int v[8] = {family, lanes, r, rw, form_bits(h), kernels, batch, ordered ? 1 : 0};
         std::memcpy(h->last_launch, v, sizeof(v));
     };
     if (!h->dense_path) {
@@ -212,110 +251,49 @@ int launch(ismpc_handle* h, int batch, const ismpc_tick_in* in, ismpc_tick_in* s
         // give the same bytes, so a late switch costs microseconds, never correctness.
         const bool recent_deferrals = h->zseen_host && *(volatile int*)h->zseen_host != 0 && lid - *(volatile int*)h->zseen_host <= 4096;
         const bool one_big = zm && (h->one_launch == 3 || (h->one_launch == 2 && !recent_deferrals));
+        auto fallback = [&](auto RR, auto SW) { tick(ismpc_tick_affine_fallback<RR, SW>, fgrid, block, 0, h->c, zm, lid); };      // (the handle's own constants, not the lane-group launch's: one instance per wavefront)
         // default for N <= 128: several instances per wavefront (ismpc_tick_quad); ISMPC_PATH=wave keeps one per wavefront
         if (h->quad_path && h->c.N <= 128) {
-            const LaneLayout lay = pick_layout(h, batch, rollout_frame < 0);      // (a closed loop driven from the host keeps the in-kernel loop's layout: same bytes)
-            const int lpi = lay.lpi;
-            DevConst cq = h->c;
-            cq.vqT = lay.vqT; cq.tzgT = lay.tzgT;
-            const int waves = (batch * lpi + 63) / 64;
-            const dim3 qgrid((waves + ISMPC_QUAD_WAVES - 1) / ISMPC_QUAD_WAVES), qblock(64 * ISMPC_QUAD_WAVES);
-            const DevConst* cdev = h->c_dev;
-            if (h->nplans) {
-                // multi-plan handle: the SW = 2 kernels read each instance's (set, plan) pair through c.sets, in the records of this launch's layout.
-                // The launch forms are a sweep's (one launch, or tick + fallback launch; never ismpc_tick_quad_inline); the lanes per instance are a
-                // plain handle's with one parameter set -- whose records are then byte-identical to a plain handle's on that plan -- and a sweep's
-                // with several
-                cq.sets = (lpi == 8 && h->sets8) ? h->sets8 : ((lpi == 32 && h->sets32) ? h->sets32 : h->c.sets);
-                if (h->sweep && lpi != 16 && lpi != 8) return fail(ISMPC_E_UNSUPPORTED, "parameter sweep: 16 or 8 lanes per instance");
-                cq.order = (h->order && h->order_batch == batch && rollout_frame < 0) ? h->order : nullptr;
-                const int form = 2 | (h->sweep ? 1 : 0);
-                quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
-                    if (one_big) {
-                        tick(ismpc_tick_quad_one<RR, LL, RW_, 2>, qgrid, qblock, 0, cq, zm, lid, cdev);
-                        note(ISMPC_KERNEL_QUAD_ONE, LL, RR, RW_, form, 1, cq.order != nullptr);
-                    } else {
-                        tick(ismpc_tick_quad<RR, LL, 2>, qgrid, qblock, 0, cq, zm, lid);
-                        note(ISMPC_KERNEL_QUAD, LL, RR, RW_, form, zm ? 2 : 1, cq.order != nullptr);
-                    }
-                });
-                if (!one_big && zm) {
-                    if (R == 1) tick(ismpc_tick_affine_fallback<1, 2>, fgrid, block, 0, h->c, zm, lid);
-                    else        tick(ismpc_tick_affine_fallback<2, 2>, fgrid, block, 0, h->c, zm, lid);
-                }
-                HIP_TRY(hipGetLastError());
-                return ISMPC_OK;
-            }
-            if (h->sweep) {
-                // parameter sweep: the per-tick kernel reads each instance's set through c.sets (16 lanes per instance, 8 beyond LPI16_BATCH)
-                if (lpi == 8) cq.sets = h->sets8;
-                cq.order = (h->order && h->order_batch == batch && rollout_frame < 0) ? h->order : nullptr;     // (ismpc_sweep_bind; per-tick launches only)
-                // (a sweep handle has 16 or 8 lanes per instance: the SW kernels are not instantiated at 32)
-                if (lpi != 16 && lpi != 8) return fail(ISMPC_E_UNSUPPORTED, "parameter sweep: 16 or 8 lanes per instance");
-                if (one_big) {
-                    quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
-                        if constexpr (LL != 32) {
-                            tick(ismpc_tick_quad_one<RR, LL, RW_, 1>, qgrid, qblock, 0, cq, zm, lid, cdev);
-                            note(ISMPC_KERNEL_QUAD_ONE, LL, RR, RW_, 1, 1, cq.order != nullptr);
+            const QuadLaunch q = quad_launch(h, batch, rollout_frame < 0);      // (a closed loop driven from the host keeps the in-kernel loop's layout: same bytes)
+            // every wavefront resident at once (<= 2 per SIMD) and a fallback to run: one launch that handles deferred instances itself (plain handles: the
+            // resident kernel has no SW instantiations)
+            const bool resident = form_bits(h) == 0 && zm && h->one_launch >= 1 && h->cus > 0 && q.waves <= 8 * h->cus;
+            // The launch forms, in this order: plain handles take ismpc_tick_quad_inline while the batch is resident; every handle then one
+            // launch (ismpc_tick_quad_one, at the tick's own three wavefronts per SIMD) or tick + fallback launch, by one_big above.  A sweep
+            // reads each instance's set through c.sets; a multi-plan handle its (set, plan) pair, in the records of this launch's layout -- its
+            // lanes per instance are a plain handle's with one parameter set (whose records are then byte-identical to a plain handle's on
+            // that plan) and a sweep's with several.
+            const int rc = with_sw(h, [&](auto SW) {
+                constexpr int sw = decltype(SW)::value;
+                return quad_shape(h->c.N, q.lpi, [&](auto RR, auto LL, auto RW_) {
+                    if constexpr (has_tick_quad(LL, sw)) {
+                        if (resident) {
+                            tick(ismpc_tick_quad_inline<RR, LL, RW_>, q.grid, q.block, 0, q.c, zm, lid, h->c_dev);
+                            note(ISMPC_KERNEL_QUAD_INLINE, LL, RR, RW_, 1, q.c.order != nullptr);
+                        } else if (one_big) {
+                            tick(ismpc_tick_quad_one<RR, LL, RW_, sw>, q.grid, q.block, 0, q.c, zm, lid, h->c_dev);
+                            note(ISMPC_KERNEL_QUAD_ONE, LL, RR, RW_, 1, q.c.order != nullptr);
+                        } else {
+                            tick(ismpc_tick_quad<RR, LL, sw>, q.grid, q.block, 0, q.c, zm, lid);
+                            if (zm) fallback(RW_, SW);              // (RW = ceil(N / 64), the fallback's own samples per lane)
+                            note(ISMPC_KERNEL_QUAD, LL, RR, RW_, zm ? 2 : 1, q.c.order != nullptr);
                         }
-                    });
-                    HIP_TRY(hipGetLastError());
-                    return ISMPC_OK;
-                }
-                quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
-                    if constexpr (LL != 32) {
-                        tick(ismpc_tick_quad<RR, LL, 1>, qgrid, qblock, 0, cq, zm, lid);
-                        note(ISMPC_KERNEL_QUAD, LL, RR, RW_, 1, zm ? 2 : 1, cq.order != nullptr);
-                    }
+                        return ISMPC_OK;
+                    } else
+                        return fail(ISMPC_E_UNSUPPORTED, "parameter sweep: 16 or 8 lanes per instance");
                 });
-                if (zm) {
-                    if (R == 1) tick(ismpc_tick_affine_fallback<1, 1>, fgrid, block, 0, h->c, zm, lid);
-                    else        tick(ismpc_tick_affine_fallback<2, 1>, fgrid, block, 0, h->c, zm, lid);
-                }
-                HIP_TRY(hipGetLastError());
-                return ISMPC_OK;
-            }
-            // every wavefront resident at once (<= 2 per SIMD) and a fallback to run: one launch that handles deferred instances itself
-            if (zm && h->one_launch >= 1 && h->cus > 0 && waves <= 8 * h->cus) {
-                quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
-                    tick(ismpc_tick_quad_inline<RR, LL, RW_>, qgrid, qblock, 0, cq, zm, lid, cdev);
-                    note(ISMPC_KERNEL_QUAD_INLINE, LL, RR, RW_, 0, 1, false);
-                });
-                HIP_TRY(hipGetLastError());
-                return ISMPC_OK;
-            }
-            if (one_big) {                  // any other batch size: one launch too, at the tick's own three wavefronts per SIMD
-                quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
-                    tick(ismpc_tick_quad_one<RR, LL, RW_, 0>, qgrid, qblock, 0, cq, zm, lid, cdev);
-                    note(ISMPC_KERNEL_QUAD_ONE, LL, RR, RW_, 0, 1, false);
-                });
-                HIP_TRY(hipGetLastError());
-                return ISMPC_OK;
-            }
-            quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
-                tick(ismpc_tick_quad<RR, LL>, qgrid, qblock, 0, cq, zm, lid);
-                note(ISMPC_KERNEL_QUAD, LL, RR, RW_, 0, zm ? 2 : 1, false);
             });
-            if (zm) {
-                if (R == 1) tick(ismpc_tick_affine_fallback<1>, fgrid, block, 0, h->c, zm, lid);
-                else        tick(ismpc_tick_affine_fallback<2>, fgrid, block, 0, h->c, zm, lid);
-            }
+            if (rc != ISMPC_OK) return rc;
             HIP_TRY(hipGetLastError());
             return ISMPC_OK;
         }
         const dim3 agrid((batch + ISMPC_AFF_WAVES - 1) / ISMPC_AFF_WAVES), ablock(64 * ISMPC_AFF_WAVES);
         auto affine = [&](auto RR) {
-            if (h->nplans) {
-                tick(ismpc_tick_affine<RR, 2>, agrid, ablock, 0, h->c, zm, lid);
-                if (zm) tick(ismpc_tick_affine_fallback<RR, 2>, fgrid, block, 0, h->c, zm, lid);
-            } else if (h->sweep) {
-                tick(ismpc_tick_affine<RR, 1>, agrid, ablock, 0, h->c, zm, lid);
-                if (zm) tick(ismpc_tick_affine_fallback<RR, 1>, fgrid, block, 0, h->c, zm, lid);
-            } else {
-                tick(ismpc_tick_affine<RR>, agrid, ablock, 0, h->c, zm, lid);
-                if (zm) tick(ismpc_tick_affine_fallback<RR>, fgrid, block, 0, h->c, zm, lid);
-            }
-            note(ISMPC_KERNEL_AFFINE, 64, RR, RR, (h->sweep ? 1 : 0) | (h->nplans ? 2 : 0), zm ? 2 : 1, false);
+            with_sw(h, [&](auto SW) {
+                tick(ismpc_tick_affine<decltype(RR)::value, decltype(SW)::value>, agrid, ablock, 0, h->c, zm, lid);
+                if (zm) fallback(RR, SW);
+            });
+            note(ISMPC_KERNEL_AFFINE, 64, RR, RR, zm ? 2 : 1, false);
         };
         if (!wave_shape(R, affine)) return fail(ISMPC_E_UNSUPPORTED, "horizon N > 256");
         HIP_TRY(hipGetLastError());
@@ -329,11 +307,203 @@ int launch(ismpc_handle* h, int batch, const ismpc_tick_in* in, ismpc_tick_in* s
         if (waves == 16)     tick(ismpc_tick_dense<RR, 16>, grid, dim3(64 * 16), lds, h->c);
         else if (waves == 8) tick(ismpc_tick_dense<RR, 8>, grid, dim3(64 * 8), lds, h->c);
         else                 tick(ismpc_tick_dense<RR, 4>, grid, dim3(64 * 4), lds, h->c);
-        note(ISMPC_KERNEL_DENSE, 64, RR, 0, 0, 1, false);
+        note(ISMPC_KERNEL_DENSE, 64, RR, 0, 1, false);
     };
     if (!wave_shape(R, dense)) return fail(ISMPC_E_UNSUPPORTED, "horizon N > 256");
     HIP_TRY(hipGetLastError());
     return ISMPC_OK;
+}
+
+// The environment as ismpc_create* finds it: every knob that is read at creation, read once.  (ISMPC_PINNED and ISMPC_HOST_ALLOC_FLAGS
+// are read by the calls they steer.)
+struct Knobs {
+    int force_waves = 0;            // ISMPC_WAVES: wavefronts per workgroup of the dense path, 4, 8 or 16 (tuning knob)
+    bool dense = false, wave = false;   // ISMPC_PATH=dense | wave
+    bool z_fallback = true;         // ISMPC_Z_FALLBACK=0: flag only, no second launch
+    int lpi = 0;                    // ISMPC_LPI: 8, 16 or 32 lanes per instance (0: not given, the layout follows the batch size)
+    bool kernel_rollout = true;     // ISMPC_ROLLOUT=host: one launch per tick
+    int one_launch = 2;             // ISMPC_ONE_LAUNCH, A/B: 0 = always two launches, 1 = one launch only for batches resident at once, 3 = always one
+    int host_mode = 3;              // ISMPC_HOST_MODE
+    int zldsq = Z_LDS_Q;            // ISMPC_Z_LDS_Q
+};
+Knobs read_knobs()
+{
+    Knobs k;
+    if (const char* fw = std::getenv("ISMPC_WAVES")) { const int v = std::atoi(fw); if (v == 4 || v == 8 || v == 16) k.force_waves = v; }
+    if (const char* pth = std::getenv("ISMPC_PATH")) { k.dense = std::strcmp(pth, "dense") == 0; k.wave = std::strcmp(pth, "wave") == 0; }
+    if (const char* zf = std::getenv("ISMPC_Z_FALLBACK")) k.z_fallback = std::atoi(zf) != 0;
+    if (const char* lp = std::getenv("ISMPC_LPI")) { const int v = std::atoi(lp); if (v == 8 || v == 16 || v == 32) k.lpi = v; }
+    if (const char* ro = std::getenv("ISMPC_ROLLOUT")) k.kernel_rollout = std::strcmp(ro, "host") != 0;
+    if (const char* fu = std::getenv("ISMPC_ONE_LAUNCH")) k.one_launch = std::max(0, std::min(3, std::atoi(fu)));
+    if (const char* hm = std::getenv("ISMPC_HOST_MODE")) k.host_mode = std::atoi(hm) & 3;
+    if (const char* e = std::getenv("ISMPC_Z_LDS_Q")) k.zldsq = std::min(Z_LDS_Q, std::max(1, std::atoi(e)));
+    return k;
+}
+
+// Everything that can be said about the arguments of ismpc_create_plans (P > 0) and ismpc_create_sweep, said before the device is touched
+int check_args(const ismpc_params* params, int K, bool sweep, const double* ftsp, int rows, int P, const Knobs& knobs)
+{
+    if (P) {
+        if (P < 1 || P > 32767) return fail(ISMPC_E_INVALID, "a multi-plan handle holds 1 .. 32767 footstep plans");
+        if (K < 1 || K > 65535) return fail(ISMPC_E_INVALID, "a multi-plan handle holds 1 .. 65535 parameter sets");
+        if (rows < 2) return fail(ISMPC_E_INVALID, "footstep plan needs at least 2 rows");
+        if ((long long)K * P > (1ll << 24)) return fail(ISMPC_E_ALLOC, "more (set, plan) pairs than one handle holds (2^24: each pair has its own anticipative tails)");
+        for (int p = 1; p < P; ++p)
+            for (int i = 0; i < rows; ++i)
+                if (std::memcmp(&ftsp[((size_t)p * rows + i) * 4 + 2], &ftsp[(size_t)i * 4 + 2], sizeof(double)) != 0)
+                    return fail(ISMPC_E_UNSUPPORTED, "multi-plan handle: plan " + std::to_string(p) + " differs from plan 0 in the z column (row " + std::to_string(i) +
+                                                     "); the plans of one handle share one height profile");
+        if (knobs.dense) return fail(ISMPC_E_UNSUPPORTED, "multi-plan handle: ISMPC_PATH=dense reads one plan");
+    }
+    if (sweep) {
+        // the sets of a sweep share what fixes the shape of the problem; everything else may differ from set to set
+        if (K < 1 || K > 65535) return fail(ISMPC_E_INVALID, "a sweep holds 1 .. 65535 parameter sets");
+        for (int k = 0; k < K; ++k) {
+            const ismpc_params& a = params[0]; const ismpc_params& b = params[k];
+            if (a.N != b.N || a.S != b.S || a.F != b.F || a.M != b.M || a.mpc_dt != b.mpc_dt || a.control_dt != b.control_dt || a.g != b.g || a.lambda_gate != b.lambda_gate)
+                return fail(ISMPC_E_INVALID, "the parameter sets of a sweep share N, S, F, M, mpc_dt, control_dt, g and lambda_gate");
+            if (!(b.mass > 0) || !(b.h_des > 0) || !(b.q_u > 0) || b.q_p < 0 || b.q_v < 0) return fail(ISMPC_E_INVALID, "sweep: mass, h_des, q_u must be positive, q_p and q_v non-negative");
+        }
+    }
+    return ISMPC_OK;
+}
+
+// upload() of each (vector, destination) pair in turn, up to the first that fails
+template <class V, class D, class... Rest> int upload_all(ismpc_handle* h, const V& v, D dst, const Rest&... rest)
+{
+    const int rc = upload(h, v, dst);
+    if constexpr (sizeof...(rest) == 0) return rc;
+    else return rc != ISMPC_OK ? rc : upload_all(h, rest...);
+}
+// DevConst records (pair records, set records, the handle's own constants) to device memory the handle owns
+int upload_records(ismpc_handle* h, const std::vector<DevConst>& recs, const DevConst** dst, const char* what)
+{
+    void* p = nullptr;
+    const size_t bytes = sizeof(DevConst) * recs.size();
+    if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(ISMPC_E_ALLOC, std::string(what) + ": records allocation failed"); }
+    h->dev_allocs.push_back(p);
+    if (hipMemcpy(p, recs.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(ISMPC_E_NO_DEVICE, std::string(what) + ": records upload failed");
+    *dst = static_cast<const DevConst*>(p);
+    return ISMPC_OK;
+}
+
+// The scalars of the constants, from the host tables
+void fill_constants(const ismpc::Tables& t, int zldsq, DevConst& c)
+{
+    c.N = t.p.N; c.NP = t.NP; c.NPs = t.NP + 2; c.S = t.p.S; c.F = t.p.F; c.nmid = t.nmid; c.npat = t.npat;
+    c.Fmax = t.Fmax; c.rows = t.rows; c.tick_divisor = t.tick_divisor;
+    c.dt = t.p.mpc_dt; c.cdt = t.p.control_dt; c.mass = t.p.mass; c.g = t.p.g; c.h_des = t.p.h_des;
+    c.half_run = t.p.foot_width / 2; c.half_first = t.p.first_step_halfwidth;
+    c.q_p = t.p.q_p; c.q_u = t.p.q_u; c.q_v = t.p.q_v; c.z_lo = t.p.z_ineq_lo; c.z_hi = t.p.z_ineq_hi;
+    c.gate = t.p.lambda_gate; c.eta = t.eta;
+    c.inv_mass = 1.0 / t.p.mass; c.dt_over_mass = t.p.mpc_dt / t.p.mass; c.inv_eta = 1.0 / t.eta;
+    c.sim_div = t.p.mpc_dt / t.p.control_dt; c.cdt_over_dt = t.p.control_dt / t.p.mpc_dt;
+    c.flat = t.flat ? 1 : 0;
+    // active-set fallback pool: 256 slots of (cap x cap + 4 cap + NT) doubles + cap ints, cap = N rows (every row may be active)
+    c.zslots = 256; c.zcap = t.p.N; c.zldsq = zldsq;
+    c.zstride = (size_t)c.zcap * c.zcap + 4 * (size_t)c.zcap + ismpc::Tables::NT + ((size_t)c.zcap + 1) / 2 + 8;
+}
+
+// The host tables, the fallback's scratch and the affine tables in the kernels' layouts, to the device.  all_layouts: the handle chooses
+// its lanes per instance per launch (or is a sweep), so the 32-lane and the 8-lane copy go beside the handle's own
+int upload_tables(ismpc_handle* h, bool all_layouts)
+{
+    const ismpc::Tables& t = h->t;
+    DevConst& c = h->c;
+    const std::vector<int> zf(4, 0), busy(c.zslots, 0); const int *zp = nullptr, *bp = nullptr;
+    int rc = upload_all(h, t.Hinv, &c.Hinv, t.W, &c.W, t.midx, &c.midx, t.midy, &c.midy, t.midz, &c.midz, t.tailx, &c.tailx, t.taily, &c.taily,
+                        t.ftsp_t, &c.ftsp_t, t.e_lo, &c.e_lo, t.ne, &c.ne, t.vtab, &c.vtab, t.tz, &c.tz, t.tg, &c.tg, t.dU, &c.dU, t.SdU, &c.SdU,
+                        t.Wt, &c.Wt, t.SW, &c.SW, t.HSt, &c.HSt, t.SHSt, &c.SHSt, zf, &zp);
+    if (rc != ISMPC_OK) return rc;
+    c.zflag = const_cast<int*>(zp);
+    {
+        // one word of page-locked host memory the kernels write the launch id to when they defer an instance (see launch())
+        void* hp = nullptr; void* dp = nullptr;
+        if (hipHostMalloc(&hp, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
+            h->zseen_host = static_cast<int*>(hp); *h->zseen_host = 0; c.zseen = static_cast<int*>(dp);
+        } else { if (hp) (void)hipHostFree(hp); (void)hipGetLastError(); c.zseen = nullptr; }
+    }
+    rc = upload(h, busy, &bp);                 // the active-set fallback pool and its slot flags
+    if (rc != ISMPC_OK) return rc;
+    c.zbusy = const_cast<int*>(bp);
+    void* pool = nullptr;
+    if (hipMalloc(&pool, c.zstride * c.zslots * sizeof(double)) != hipSuccess) return fail(ISMPC_E_ALLOC, "fallback pool allocation failed");
+    h->dev_allocs.push_back(pool); c.zpool = static_cast<double*>(pool);
+    constexpr int NTq = ismpc::Tables::NT;
+    const size_t npp = t.vtab.size() / (6 * (size_t)NTq);
+    std::vector<double> vq(t.vtab.size()), tzg(2 * (size_t)NTq), mxy(2 * t.midx.size());
+    for (size_t pp = 0; pp < npp; ++pp)
+        for (int k = 0; k < 6; ++k)
+            for (int n = 0; n < NTq; ++n) vq[(pp * NTq + n) * 6 + k] = t.vtab[(pp * 6 + k) * NTq + n];
+    for (int n = 0; n < NTq; ++n) { tzg[2 * n] = t.tz[n]; tzg[2 * n + 1] = t.tg[n]; }
+    for (size_t n = 0; n < t.midx.size(); ++n) { mxy[2 * n] = t.midx[n]; mxy[2 * n + 1] = t.midy[n]; }
+    rc = upload_all(h, vq, &c.vq, tzg, &c.tzg, mxy, &c.midxy);
+    // lane-contiguous copies for the lane-group kernels' shapes (sample li*R + r of pattern p): the handle's layout and,
+    // when the layout is chosen per launch, the 32-lane and the 8-lane one beside it
+    const int layouts = t.p.N > 128 ? 0 : (all_layouts ? 3 : 1);
+    for (int pass = 0; pass < layouts && rc == ISMPC_OK; ++pass) {
+        const int lpi = pass == 0 ? h->lpi : (pass == 1 ? 32 : 8);
+        std::vector<double> vqT, tzgT;
+        ismpc::lane_group_tables(t, lpi, quad_R(t.p.N, lpi), vqT, tzgT);
+        rc = upload_all(h, vqT, pass == 0 ? &c.vqT : (pass == 1 ? &h->vqT32 : &h->vqT8), tzgT, pass == 0 ? &c.tzgT : (pass == 1 ? &h->tzgT32 : &h->tzgT8));
+    }
+    return rc;
+}
+
+// Multi-plan handles, part 1: every plan's tables side by side on the device -- midx, midy, midxy (the lane-group kernels' window), the
+// step timings and, with ONE parameter set, the host-built tails (with several the tails are built on the device per pair: sweep_build)
+struct PlanSlabs { const double *midx = nullptr, *midy = nullptr, *midxy = nullptr, *t = nullptr, *tailx = nullptr, *taily = nullptr; };
+int upload_plans(ismpc_handle* h, const ismpc_params& p0, const double* ftsp, PlanSlabs& pl)
+{
+    const int P = h->nplans, rows = h->t.rows; const bool sweep = h->sweep;
+    const size_t nm = (size_t)h->t.nmid;
+    std::vector<double> mxy(2 * nm * P), tt((size_t)rows * P), tx(sweep ? 0 : nm * P), ty(sweep ? 0 : nm * P);
+    h->pl_midx.resize(nm * P); h->pl_midy.resize(nm * P);
+    for (int p = 0; p < P; ++p) {
+        ismpc::PlanTables pt;
+        ismpc::build_plan_tables(p0, ftsp + (size_t)p * rows * 4, rows, pt);
+        std::copy(pt.midx.begin(), pt.midx.end(), h->pl_midx.begin() + p * nm); std::copy(pt.midy.begin(), pt.midy.end(), h->pl_midy.begin() + p * nm);
+        for (size_t n = 0; n < nm; ++n) { mxy[2 * (p * nm + n)] = pt.midx[n]; mxy[2 * (p * nm + n) + 1] = pt.midy[n]; }
+        std::copy(pt.ftsp_t.begin(), pt.ftsp_t.end(), tt.begin() + (size_t)p * rows);
+        if (!sweep) { std::copy(pt.tailx.begin(), pt.tailx.end(), tx.begin() + p * nm); std::copy(pt.taily.begin(), pt.taily.end(), ty.begin() + p * nm); }
+    }
+    const int rc = upload_all(h, h->pl_midx, &pl.midx, h->pl_midy, &pl.midy, mxy, &pl.midxy, tt, &pl.t);
+    return (rc != ISMPC_OK || sweep) ? rc : upload_all(h, tx, &pl.tailx, ty, &pl.taily);
+}
+// ... part 2: one record per (set, plan) pair, set-major -- the set's record (`base`) with the plan's tables in place of plan 0's
+std::vector<DevConst> pair_records(const ismpc_handle* h, const std::vector<DevConst>& base, const PlanSlabs& pl)
+{
+    const int P = h->nplans;
+    const size_t nm = (size_t)h->t.nmid, rows = (size_t)h->t.rows;
+    std::vector<DevConst> pr(base.size() * (size_t)P);
+    for (size_t k = 0; k < base.size(); ++k)
+        for (int p = 0; p < P; ++p) {
+            DevConst& d = pr[k * P + p]; d = base[k];
+            d.midx = pl.midx + p * nm; d.midy = pl.midy + p * nm; d.midxy = pl.midxy + 2 * p * nm; d.ftsp_t = pl.t + p * rows;
+            if (h->sweep) { d.tailx = h->sw.tailx + (k * P + p) * h->sw.s_tail; d.taily = h->sw.taily + (k * P + p) * h->sw.s_tail; }
+            else { d.tailx = pl.tailx + p * nm; d.taily = pl.taily + p * nm; }
+            d.sets = nullptr; d.nsets = 0; d.nplans = 0; d.order = nullptr;
+        }
+    return pr;
+}
+// One DevConst record per set of a sweep: the handle's, with the set's scalars and device-built table pointers in place of set 0's host-built ones
+std::vector<DevConst> sweep_records(const ismpc_handle* h, const ismpc_params* params, int K)
+{
+    std::vector<DevConst> cs((size_t)K, h->c);
+    for (int k = 0; k < K; ++k) {
+        DevConst& d = cs[k]; const ismpc_params& q = params[k];
+        const double eta = std::sqrt(q.g / q.h_des);
+        d.mass = q.mass; d.h_des = q.h_des; d.half_run = q.foot_width / 2; d.half_first = q.first_step_halfwidth;
+        d.q_p = q.q_p; d.q_u = q.q_u; d.q_v = q.q_v; d.z_lo = q.z_ineq_lo; d.z_hi = q.z_ineq_hi; d.eta = eta;
+        d.inv_mass = 1.0 / q.mass; d.dt_over_mass = q.mpc_dt / q.mass; d.inv_eta = 1.0 / eta;
+        d.vtab = h->sw.vtab + (size_t)k * h->sw.s_vtab; d.vqT = h->sw.vqT + (size_t)k * h->sw.s_vqT;
+        d.Wt = h->sw.Wt + (size_t)k * h->sw.s_W; d.SW = h->sw.SW + (size_t)k * h->sw.s_W;
+        d.HSt = h->sw.HSt + (size_t)k * h->sw.s_HS; d.SHSt = h->sw.SHSt + (size_t)k * h->sw.s_HS;
+        if (h->sw.dU) { d.dU = h->sw.dU + (size_t)k * h->sw.s_dU; d.SdU = h->sw.SdU + (size_t)k * h->sw.s_dU; }      // (plans with mid_z != 0)
+        d.tailx = h->sw.tailx + (size_t)k * h->plans() * h->sw.s_tail; d.taily = h->sw.taily + (size_t)k * h->plans() * h->sw.s_tail;
+        d.Hinv = nullptr; d.W = nullptr; d.vq = nullptr; d.sets = nullptr; d.nsets = 0;
+    }
+    return cs;
 }
 
 }  // namespace
@@ -365,256 +535,75 @@ static int create_impl(const ismpc_params* params, int K, bool sweep, const doub
 {
     if (!params || !ftsp || !out) return fail(ISMPC_E_INVALID, "null argument");
     *out = nullptr;
-    if (P) {
-        // everything that can be said about the arguments is said before the device is touched
-        if (P < 1 || P > 32767) return fail(ISMPC_E_INVALID, "a multi-plan handle holds 1 .. 32767 footstep plans");
-        if (K < 1 || K > 65535) return fail(ISMPC_E_INVALID, "a multi-plan handle holds 1 .. 65535 parameter sets");
-        if (rows < 2) return fail(ISMPC_E_INVALID, "footstep plan needs at least 2 rows");
-        if ((long long)K * P > (1ll << 24)) return fail(ISMPC_E_ALLOC, "more (set, plan) pairs than one handle holds (2^24: each pair has its own anticipative tails)");
-        for (int p = 1; p < P; ++p)
-            for (int i = 0; i < rows; ++i)
-                if (std::memcmp(&ftsp[((size_t)p * rows + i) * 4 + 2], &ftsp[(size_t)i * 4 + 2], sizeof(double)) != 0)
-                    return fail(ISMPC_E_UNSUPPORTED, "multi-plan handle: plan " + std::to_string(p) + " differs from plan 0 in the z column (row " + std::to_string(i) +
-                                                     "); the plans of one handle share one height profile");
-        if (const char* pth = std::getenv("ISMPC_PATH"))
-            if (std::strcmp(pth, "dense") == 0) return fail(ISMPC_E_UNSUPPORTED, "multi-plan handle: ISMPC_PATH=dense reads one plan");
-    }
-    if (sweep) {
-        // the sets of a sweep share what fixes the shape of the problem; everything else may differ from set to set
-        if (K < 1 || K > 65535) return fail(ISMPC_E_INVALID, "a sweep holds 1 .. 65535 parameter sets");
-        for (int k = 0; k < K; ++k) {
-            const ismpc_params& a = params[0]; const ismpc_params& b = params[k];
-            if (a.N != b.N || a.S != b.S || a.F != b.F || a.M != b.M || a.mpc_dt != b.mpc_dt || a.control_dt != b.control_dt || a.g != b.g || a.lambda_gate != b.lambda_gate)
-                return fail(ISMPC_E_INVALID, "the parameter sets of a sweep share N, S, F, M, mpc_dt, control_dt, g and lambda_gate");
-            if (!(b.mass > 0) || !(b.h_des > 0) || !(b.q_u > 0) || b.q_p < 0 || b.q_v < 0) return fail(ISMPC_E_INVALID, "sweep: mass, h_des, q_u must be positive, q_p and q_v non-negative");
-        }
-    }
+    const Knobs knobs = read_knobs();
+    int rc = check_args(params, K, sweep, ftsp, rows, P, knobs);
+    if (rc != ISMPC_OK) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(ISMPC_E_NO_DEVICE, "no HIP device visible: the ISMPC hot path has no CPU fallback");
     if (device < 0 || device >= ndev) return fail(ISMPC_E_INVALID, "device ordinal out of range");
-    ismpc_handle* h = new (std::nothrow) ismpc_handle();
+    // the handle is destroyed on every way out but the last
+    std::unique_ptr<ismpc_handle, void (*)(ismpc_handle*)> owner(new (std::nothrow) ismpc_handle(), ismpc_destroy);
+    ismpc_handle* h = owner.get();
     if (!h) return fail(ISMPC_E_ALLOC, "out of host memory");
-    std::string err;
-    int rc = ismpc::build_tables(*params, ftsp, rows, h->t, err);
-    if (rc != ISMPC_OK) { delete h; return fail(rc, err); }
     h->device = device;
-    if (const char* fw = std::getenv("ISMPC_WAVES")) {            // tuning knob: wavefronts per workgroup
-        const int v = std::atoi(fw);
-        if (v == 4 || v == 8 || v == 16) h->force_waves = v;
-    }
-    if (const char* pth = std::getenv("ISMPC_PATH")) { h->dense_path = std::strcmp(pth, "dense") == 0; h->quad_path = std::strcmp(pth, "wave") != 0 && !h->dense_path; }
-    if (const char* zf = std::getenv("ISMPC_Z_FALLBACK")) h->z_fallback = std::atoi(zf) != 0;   // 0: flag only, no second launch
-    if (const char* lp = std::getenv("ISMPC_LPI")) { const int v = std::atoi(lp); if (v == 8 || v == 16 || v == 32) { h->lpi = v; h->lpi_auto = false; } }
-    if (const char* ro = std::getenv("ISMPC_ROLLOUT")) h->kernel_rollout = std::strcmp(ro, "host") != 0;
+    std::string err;
+    rc = ismpc::build_tables(*params, ftsp, rows, h->t, err);
+    if (rc != ISMPC_OK) return fail(rc, err);
+    h->force_waves = knobs.force_waves; h->dense_path = knobs.dense; h->quad_path = !knobs.dense && !knobs.wave;
+    h->z_fallback = knobs.z_fallback; h->kernel_rollout = knobs.kernel_rollout; h->one_launch = knobs.one_launch; h->host_mode = knobs.host_mode;
+    if (knobs.lpi) { h->lpi = knobs.lpi; h->lpi_auto = false; }
+    h->nplans = P;
     if (sweep) {      // one kernel shape: 16 lanes per instance (ISMPC_Z_FALLBACK=0 still means flag-only: bench.py times the tick kernel alone with it)
         h->sweep = true; h->lpi = 16; h->lpi_auto = false; h->quad_path = true; h->dense_path = false;
         h->sets.assign(params, params + K); h->ftsp.assign(ftsp, ftsp + (size_t)rows * 4);
     }
     DeviceGuard guard_(device);
-    if (guard_.err != hipSuccess) { delete h; return fail(ISMPC_E_NO_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(guard_.err)); }
+    if (guard_.err != hipSuccess) return fail(ISMPC_E_NO_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(guard_.err));
     { hipDeviceProp_t prop; h->cus = (hipGetDeviceProperties(&prop, device) == hipSuccess) ? prop.multiProcessorCount : 0; }
-    if (const char* fu = std::getenv("ISMPC_ONE_LAUNCH")) h->one_launch = std::max(0, std::min(3, std::atoi(fu)));    // A/B: 0 = always two launches, 1 = one launch only for batches resident at once, 3 = always one    // 0: always two launches (A/B)
-    const ismpc::Tables& t = h->t;
-    DevConst& c = h->c;
-    c.N = t.p.N; c.NP = t.NP; c.NPs = t.NP + 2; c.S = t.p.S; c.F = t.p.F; c.nmid = t.nmid; c.npat = t.npat;
-    c.Fmax = t.Fmax; c.rows = t.rows; c.tick_divisor = t.tick_divisor;
-    c.dt = t.p.mpc_dt; c.cdt = t.p.control_dt; c.mass = t.p.mass; c.g = t.p.g; c.h_des = t.p.h_des;
-    c.half_run = t.p.foot_width / 2; c.half_first = t.p.first_step_halfwidth;
-    c.q_p = t.p.q_p; c.q_u = t.p.q_u; c.q_v = t.p.q_v; c.z_lo = t.p.z_ineq_lo; c.z_hi = t.p.z_ineq_hi;
-    c.gate = t.p.lambda_gate; c.eta = t.eta;
-    c.inv_mass = 1.0 / t.p.mass; c.dt_over_mass = t.p.mpc_dt / t.p.mass; c.inv_eta = 1.0 / t.eta;
-    c.sim_div = t.p.mpc_dt / t.p.control_dt; c.cdt_over_dt = t.p.control_dt / t.p.mpc_dt;
-    rc = upload(h, t.Hinv, &c.Hinv);
-    if (rc == ISMPC_OK) rc = upload(h, t.W, &c.W);
-    if (rc == ISMPC_OK) rc = upload(h, t.midx, &c.midx);
-    if (rc == ISMPC_OK) rc = upload(h, t.midy, &c.midy);
-    if (rc == ISMPC_OK) rc = upload(h, t.midz, &c.midz);
-    if (rc == ISMPC_OK) rc = upload(h, t.tailx, &c.tailx);
-    if (rc == ISMPC_OK) rc = upload(h, t.taily, &c.taily);
-    if (rc == ISMPC_OK) rc = upload(h, t.ftsp_t, &c.ftsp_t);
-    if (rc == ISMPC_OK) rc = upload(h, t.e_lo, &c.e_lo);
-    if (rc == ISMPC_OK) rc = upload(h, t.ne, &c.ne);
-    if (rc == ISMPC_OK) rc = upload(h, t.vtab, &c.vtab);
-    if (rc == ISMPC_OK) rc = upload(h, t.tz, &c.tz);
-    if (rc == ISMPC_OK) rc = upload(h, t.tg, &c.tg);
-    if (rc == ISMPC_OK) rc = upload(h, t.dU, &c.dU);
-    if (rc == ISMPC_OK) rc = upload(h, t.SdU, &c.SdU);
-    if (rc == ISMPC_OK) rc = upload(h, t.Wt, &c.Wt);
-    if (rc == ISMPC_OK) rc = upload(h, t.SW, &c.SW);
-    if (rc == ISMPC_OK) rc = upload(h, t.HSt, &c.HSt);
-    if (rc == ISMPC_OK) rc = upload(h, t.SHSt, &c.SHSt);
-    if (rc == ISMPC_OK) { std::vector<int> zf(4, 0); const int* zp = nullptr; rc = upload(h, zf, &zp); c.zflag = const_cast<int*>(zp); }
-    if (rc == ISMPC_OK) {
-        // one word of page-locked host memory the kernels write the launch id to when they defer an instance (see launch())
-        void* hp = nullptr; void* dp = nullptr;
-        if (hipHostMalloc(&hp, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
-            h->zseen_host = static_cast<int*>(hp); *h->zseen_host = 0; c.zseen = static_cast<int*>(dp);
-        } else { if (hp) (void)hipHostFree(hp); (void)hipGetLastError(); c.zseen = nullptr; }
-    }
-    if (rc == ISMPC_OK) {
-        // active-set fallback pool: 256 slots of (cap x cap + 4 cap + NT) doubles + cap ints, cap = N rows (every row may be active)
-        c.zslots = 256; c.zcap = t.p.N; c.zldsq = Z_LDS_Q;
-        if (const char* e = std::getenv("ISMPC_Z_LDS_Q")) c.zldsq = std::min(Z_LDS_Q, std::max(1, std::atoi(e)));
-        c.zstride = (size_t)c.zcap * c.zcap + 4 * (size_t)c.zcap + ismpc::Tables::NT + ((size_t)c.zcap + 1) / 2 + 8;
-        std::vector<int> busy(c.zslots, 0); const int* bp = nullptr;
-        rc = upload(h, busy, &bp); c.zbusy = const_cast<int*>(bp);
-        if (rc == ISMPC_OK) {
-            void* zp = nullptr;
-            if (hipMalloc(&zp, c.zstride * c.zslots * sizeof(double)) != hipSuccess) rc = fail(ISMPC_E_ALLOC, "fallback pool allocation failed");
-            else { h->dev_allocs.push_back(zp); c.zpool = static_cast<double*>(zp); }
-        }
-    }
-    if (rc == ISMPC_OK) {
-        constexpr int NTq = ismpc::Tables::NT;
-        const size_t npp = t.vtab.size() / (6 * (size_t)NTq);
-        std::vector<double> vq(t.vtab.size()), tzg(2 * (size_t)NTq), mxy(2 * t.midx.size());
-        for (size_t pp = 0; pp < npp; ++pp)
-            for (int k = 0; k < 6; ++k)
-                for (int n = 0; n < NTq; ++n) vq[(pp * NTq + n) * 6 + k] = t.vtab[(pp * 6 + k) * NTq + n];
-        for (int n = 0; n < NTq; ++n) { tzg[2 * n] = t.tz[n]; tzg[2 * n + 1] = t.tg[n]; }
-        for (size_t n = 0; n < t.midx.size(); ++n) { mxy[2 * n] = t.midx[n]; mxy[2 * n + 1] = t.midy[n]; }
-        rc = upload(h, vq, &c.vq);
-        if (rc == ISMPC_OK) rc = upload(h, tzg, &c.tzg);
-        if (rc == ISMPC_OK) rc = upload(h, mxy, &c.midxy);
-        if (rc == ISMPC_OK && t.p.N <= 128) {
-            // lane-contiguous copies for the lane-group kernels' shapes (sample li*R + r of pattern p): the handle's layout and,
-            // when the layout is chosen per launch, the 32-lane and the 8-lane one beside it
-            for (int pass = 0; pass < ((h->lpi_auto || sweep) ? 3 : 1) && rc == ISMPC_OK; ++pass) {
-                const int lpi = pass == 0 ? h->lpi : (pass == 1 ? 32 : 8), R = quad_R(t.p.N, lpi);
-                std::vector<double> vqT(npp * (size_t)R * 3 * lpi * 2), tzgT((size_t)R * lpi * 2);
-                for (size_t pp = 0; pp < npp; ++pp)
-                    for (int r = 0; r < R; ++r)
-                        for (int k = 0; k < 3; ++k)
-                            for (int li = 0; li < lpi; ++li) {
-                                const int n = li * R + r;                       // < 128 <= NT
-                                const size_t dst = (((pp * R + r) * 3 + k) * lpi + li) * 2;
-                                vqT[dst] = vq[(pp * NTq + n) * 6 + 2 * k]; vqT[dst + 1] = vq[(pp * NTq + n) * 6 + 2 * k + 1];
-                            }
-                for (int r = 0; r < R; ++r)
-                    for (int li = 0; li < lpi; ++li) { const int n = li * R + r; tzgT[((size_t)r * lpi + li) * 2] = t.tz[n]; tzgT[((size_t)r * lpi + li) * 2 + 1] = t.tg[n]; }
-                rc = upload(h, vqT, pass == 0 ? &c.vqT : (pass == 1 ? &h->vqT32 : &h->vqT8));
-                if (rc == ISMPC_OK) rc = upload(h, tzgT, pass == 0 ? &c.tzgT : (pass == 1 ? &h->tzgT32 : &h->tzgT8));
-            }
-        }
-    }
-    c.flat = t.flat ? 1 : 0;
-    if (rc != ISMPC_OK) { ismpc_destroy(h); return rc; }
-    if (const char* hm = std::getenv("ISMPC_HOST_MODE")) h->host_mode = std::atoi(hm) & 3;
+    fill_constants(h->t, knobs.zldsq, h->c);
+    rc = upload_tables(h, h->lpi_auto || sweep);
+    if (rc != ISMPC_OK) return rc;
     if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess ||
-        hipEventCreate(&h->ev1) != hipSuccess) { ismpc_destroy(h); return fail(ISMPC_E_NO_DEVICE, "stream/event creation failed"); }
-    // multi-plan handle, part 1: every plan's tables side by side on the device -- midx, midy, midxy (the lane-group kernels' window),
-    // the step timings and, with ONE parameter set, the host-built tails (with several the tails are built on the device per pair, below)
-    const double *pl_midx = nullptr, *pl_midy = nullptr, *pl_midxy = nullptr, *pl_t = nullptr, *pl_tailx = nullptr, *pl_taily = nullptr;
-    if (P) {
-        const size_t nm = (size_t)t.nmid;
-        std::vector<double> mxy(2 * nm * P), tt((size_t)rows * P), tx(sweep ? 0 : nm * P), ty(sweep ? 0 : nm * P);
-        h->pl_midx.resize(nm * P); h->pl_midy.resize(nm * P);
-        for (int p = 0; p < P; ++p) {
-            ismpc::PlanTables pt;
-            ismpc::build_plan_tables(params[0], ftsp + (size_t)p * rows * 4, rows, pt);
-            std::copy(pt.midx.begin(), pt.midx.end(), h->pl_midx.begin() + p * nm); std::copy(pt.midy.begin(), pt.midy.end(), h->pl_midy.begin() + p * nm);
-            for (size_t n = 0; n < nm; ++n) { mxy[2 * (p * nm + n)] = pt.midx[n]; mxy[2 * (p * nm + n) + 1] = pt.midy[n]; }
-            std::copy(pt.ftsp_t.begin(), pt.ftsp_t.end(), tt.begin() + (size_t)p * rows);
-            if (!sweep) { std::copy(pt.tailx.begin(), pt.tailx.end(), tx.begin() + p * nm); std::copy(pt.taily.begin(), pt.taily.end(), ty.begin() + p * nm); }
-        }
-        rc = upload(h, h->pl_midx, &pl_midx);
-        if (rc == ISMPC_OK) rc = upload(h, h->pl_midy, &pl_midy);
-        if (rc == ISMPC_OK) rc = upload(h, mxy, &pl_midxy);
-        if (rc == ISMPC_OK) rc = upload(h, tt, &pl_t);
-        if (rc == ISMPC_OK && !sweep) rc = upload(h, tx, &pl_tailx);
-        if (rc == ISMPC_OK && !sweep) rc = upload(h, ty, &pl_taily);
-        if (rc != ISMPC_OK) { ismpc_destroy(h); return rc; }
-    }
-    // ... part 2: one record per (set, plan) pair, set-major -- the set's record (`base`) with the plan's tables in place of plan 0's
-    auto upload_pairs = [&](const std::vector<DevConst>& base, const DevConst** dst) -> int {
-        const size_t nm = (size_t)t.nmid;
-        std::vector<DevConst> pr(base.size() * (size_t)P);
-        for (size_t k = 0; k < base.size(); ++k)
-            for (int p = 0; p < P; ++p) {
-                DevConst& d = pr[k * P + p]; d = base[k];
-                d.midx = pl_midx + p * nm; d.midy = pl_midy + p * nm; d.midxy = pl_midxy + 2 * p * nm; d.ftsp_t = pl_t + (size_t)p * rows;
-                if (sweep) { d.tailx = h->sw.tailx + (k * P + p) * h->sw.s_tail; d.taily = h->sw.taily + (k * P + p) * h->sw.s_tail; }
-                else { d.tailx = pl_tailx + p * nm; d.taily = pl_taily + p * nm; }
-                d.sets = nullptr; d.nsets = 0; d.nplans = 0; d.order = nullptr;
-            }
-        void* sp = nullptr;
-        if (hipMalloc(&sp, sizeof(DevConst) * pr.size()) != hipSuccess) { (void)hipGetLastError(); return fail(ISMPC_E_ALLOC, "multi-plan handle: pair records allocation failed"); }
-        h->dev_allocs.push_back(sp);
-        if (hipMemcpy(sp, pr.data(), sizeof(DevConst) * pr.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(ISMPC_E_NO_DEVICE, "multi-plan handle: pair records upload failed");
-        *dst = static_cast<const DevConst*>(sp);
-        return ISMPC_OK;
-    };
-    if (P && !sweep) {
-        // one parameter set: the pair records are the handle's own constants per plan, once per lane layout it may launch with
-        const DevConst* recs = nullptr;
-        std::vector<DevConst> base(1, h->c);
-        rc = upload_pairs(base, &recs);
-        if (rc == ISMPC_OK && h->vqT32) { base[0].vqT = h->vqT32; rc = upload_pairs(base, &h->sets32); }
-        if (rc == ISMPC_OK && h->vqT8) { base[0].vqT = h->vqT8; rc = upload_pairs(base, &h->sets8); }
-        if (rc != ISMPC_OK) { ismpc_destroy(h); return rc; }
-        h->c.sets = recs; h->c.nsets = 1; h->c.nplans = P; h->nplans = P;
-    }
+        hipEventCreate(&h->ev1) != hipSuccess) return fail(ISMPC_E_NO_DEVICE, "stream/event creation failed");
+    PlanSlabs pl;
+    if (P) rc = upload_plans(h, params[0], ftsp, pl);
+    if (rc != ISMPC_OK) return rc;
+    // the records c.sets points to: per set for a sweep, per (set, plan) pair for a multi-plan handle
+    auto records = [&](const std::vector<DevConst>& base) { return P ? pair_records(h, base, pl) : base; };
+    const char* what = P ? "multi-plan handle" : "sweep";
+    const DevConst* recs = nullptr;
     if (sweep) {
-        // every set's tables, built on the device (MFMA Newton-Schulz inverse of the K vertical Hessians, csrc/ismpc_sweep.hip), and one
-        // DevConst record per set: the handle's, with the set's scalars and table pointers in place of set 0's host-built ones
+        // every set's tables, built on the device (MFMA Newton-Schulz inverse of the K vertical Hessians, csrc/ismpc_sweep.hip)
         std::string serr;
         // 8 lanes per instance beyond LPI16_BATCH, as plain handles take them (ISMPC_LPI=16 keeps 16 at every size).  With eight instances
         // of a wavefront reading eight sets' tables it measured level to 2 % slower on the 64-set batch (round 3: 9.25-9.28 against
         // 9.27-9.43e8 ticks/s); with the batch sorted by set (ismpc_sweep_bind: one set per wavefront) it is 5 % faster (round 4: 9.65-9.71
         // against 9.17-9.26e8), so it is the default now
-        const char* lp8 = std::getenv("ISMPC_LPI");
-        const bool lanes8 = !(lp8 && std::atoi(lp8) == 16);
-        rc = ismpc::sweep_build(params, K, h->t, P ? pl_midx : c.midx, P ? pl_midy : c.midy, c.midz, c.e_lo, c.ne, 16, quad_R(t.p.N, 16), lanes8 ? 8 : 0, quad_R(t.p.N, 8), h->own_stream, h->sw, h->dev_allocs, serr,
-                                P ? P : 1);
-        if (rc != ISMPC_OK) { ismpc_destroy(h); return fail(rc, serr); }
-        std::vector<DevConst> cs((size_t)K, h->c);
-        for (int k = 0; k < K; ++k) {
-            DevConst& d = cs[k]; const ismpc_params& q = params[k];
-            const double eta = std::sqrt(q.g / q.h_des);
-            d.mass = q.mass; d.h_des = q.h_des; d.half_run = q.foot_width / 2; d.half_first = q.first_step_halfwidth;
-            d.q_p = q.q_p; d.q_u = q.q_u; d.q_v = q.q_v; d.z_lo = q.z_ineq_lo; d.z_hi = q.z_ineq_hi; d.eta = eta;
-            d.inv_mass = 1.0 / q.mass; d.dt_over_mass = q.mpc_dt / q.mass; d.inv_eta = 1.0 / eta;
-            d.vtab = h->sw.vtab + (size_t)k * h->sw.s_vtab; d.vqT = h->sw.vqT + (size_t)k * h->sw.s_vqT;
-            d.Wt = h->sw.Wt + (size_t)k * h->sw.s_W; d.SW = h->sw.SW + (size_t)k * h->sw.s_W;
-            d.HSt = h->sw.HSt + (size_t)k * h->sw.s_HS; d.SHSt = h->sw.SHSt + (size_t)k * h->sw.s_HS;
-            if (h->sw.dU) { d.dU = h->sw.dU + (size_t)k * h->sw.s_dU; d.SdU = h->sw.SdU + (size_t)k * h->sw.s_dU; }      // (plans with mid_z != 0)
-            d.tailx = h->sw.tailx + (size_t)k * (P ? P : 1) * h->sw.s_tail; d.taily = h->sw.taily + (size_t)k * (P ? P : 1) * h->sw.s_tail;
-            d.Hinv = nullptr; d.W = nullptr; d.vq = nullptr; d.sets = nullptr; d.nsets = 0;
-        }
-        if (P) {
-            // several sets x several plans: the pair records over the sets' device-built records (16 lanes and, beside them, 8)
-            const DevConst* recs = nullptr;
-            rc = upload_pairs(cs, &recs);
-            if (rc == ISMPC_OK && h->sw.vqT2) {
-                for (int k = 0; k < K; ++k) cs[k].vqT = h->sw.vqT2 + (size_t)k * h->sw.s_vqT2;
-                rc = upload_pairs(cs, &h->sets8);
-            }
-            if (rc != ISMPC_OK) { ismpc_destroy(h); return rc; }
-            h->c.sets = recs; h->c.nsets = K; h->c.nplans = P; h->nplans = P;
-        } else {
-        void* sp = nullptr;
-        if (hipMalloc(&sp, sizeof(DevConst) * (size_t)K) != hipSuccess) { ismpc_destroy(h); return fail(ISMPC_E_ALLOC, "sweep: set records allocation failed"); }
-        h->dev_allocs.push_back(sp);
-        if (hipMemcpy(sp, cs.data(), sizeof(DevConst) * (size_t)K, hipMemcpyHostToDevice) != hipSuccess) { ismpc_destroy(h); return fail(ISMPC_E_NO_DEVICE, "sweep: set records upload failed"); }
-        h->c.sets = static_cast<const DevConst*>(sp); h->c.nsets = K;
-        if (h->sw.vqT2) {                                      // the same records over the 8-lane copy of the affine tables (pick_layout)
+        const bool lanes8 = knobs.lpi != 16;
+        rc = ismpc::sweep_build(params, K, h->t, P ? pl.midx : h->c.midx, P ? pl.midy : h->c.midy, h->c.midz, h->c.e_lo, h->c.ne, 16, quad_R(h->c.N, 16), lanes8 ? 8 : 0, quad_R(h->c.N, 8),
+                                h->own_stream, h->sw, h->dev_allocs, serr, h->plans());
+        if (rc != ISMPC_OK) return fail(rc, serr);
+        // the set records over the 16-lane copy of the affine tables and, beside them, over the 8-lane copy (pick_layout)
+        std::vector<DevConst> cs = sweep_records(h, params, K);
+        rc = upload_records(h, records(cs), &recs, what);
+        if (rc == ISMPC_OK && h->sw.vqT2) {
             for (int k = 0; k < K; ++k) cs[k].vqT = h->sw.vqT2 + (size_t)k * h->sw.s_vqT2;
-            void* sp8 = nullptr;
-            if (hipMalloc(&sp8, sizeof(DevConst) * (size_t)K) != hipSuccess) { ismpc_destroy(h); return fail(ISMPC_E_ALLOC, "sweep: set records allocation failed"); }
-            h->dev_allocs.push_back(sp8);
-            if (hipMemcpy(sp8, cs.data(), sizeof(DevConst) * (size_t)K, hipMemcpyHostToDevice) != hipSuccess) { ismpc_destroy(h); return fail(ISMPC_E_NO_DEVICE, "sweep: set records upload failed"); }
-            h->sets8 = static_cast<const DevConst*>(sp8);
+            rc = upload_records(h, records(cs), &h->sets8, what);
         }
-        }
+    } else if (P) {
+        // one parameter set: the pair records are the handle's own constants per plan, once per lane layout it may launch with
+        std::vector<DevConst> base(1, h->c);
+        rc = upload_records(h, records(base), &recs, what);
+        if (rc == ISMPC_OK && h->vqT32) { base[0].vqT = h->vqT32; rc = upload_records(h, records(base), &h->sets32, what); }
+        if (rc == ISMPC_OK && h->vqT8) { base[0].vqT = h->vqT8; rc = upload_records(h, records(base), &h->sets8, what); }
     }
-    {
-        void* cp = nullptr;
-        if (hipMalloc(&cp, sizeof(DevConst)) != hipSuccess) { ismpc_destroy(h); return fail(ISMPC_E_ALLOC, "constants allocation failed"); }
-        h->dev_allocs.push_back(cp); h->c_dev = static_cast<DevConst*>(cp);
-        if (hipMemcpy(cp, &h->c, sizeof(DevConst), hipMemcpyHostToDevice) != hipSuccess) { ismpc_destroy(h); return fail(ISMPC_E_NO_DEVICE, "constants upload failed"); }
-    }
-    *out = h;
+    if (rc != ISMPC_OK) return rc;
+    if (recs) { h->c.sets = recs; h->c.nsets = K; h->c.nplans = P; }
+    // the constants in device memory, last: with everything above in them
+    rc = upload_records(h, std::vector<DevConst>(1, h->c), &h->c_dev, "constants");
+    if (rc != ISMPC_OK) return rc;
+    *out = owner.release();
     return ISMPC_OK;
 }
 
@@ -637,13 +626,13 @@ int ismpc_create_plans(const ismpc_params* params, int n_sets, const double* fts
 int ismpc_plans_info(const ismpc_handle* h, int* n_plans)
 {
     if (!h || !n_plans) return fail(ISMPC_E_INVALID, "null argument");
-    *n_plans = h->nplans ? h->nplans : 1;
+    *n_plans = h->plans();
     return ISMPC_OK;
 }
 
 int ismpc_get_midpoint_plan(const ismpc_handle* h, int plan, double* dst, int capacity_rows)
 {
-    if (!h || !dst || capacity_rows < h->t.nmid || plan < 0 || plan >= (h->nplans ? h->nplans : 1)) return fail(ISMPC_E_INVALID, "bad argument");
+    if (!h || !dst || capacity_rows < h->t.nmid || plan < 0 || plan >= h->plans()) return fail(ISMPC_E_INVALID, "bad argument");
     if (!h->nplans) return ismpc_get_midpoint(h, dst, capacity_rows);
     const size_t o = (size_t)plan * h->t.nmid;
     for (int i = 0; i < h->t.nmid; ++i) { dst[3*i] = h->pl_midx[o + i]; dst[3*i+1] = h->pl_midy[o + i]; dst[3*i+2] = h->t.midz[i]; }
@@ -657,7 +646,7 @@ int ismpc_sweep_bind(ismpc_handle* h, int batch, const ismpc_tick_in* in_dev, vo
     ON_DEVICE(h);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (batch == 0) { h->order_batch = 0; return ISMPC_OK; }
-    const int nb = h->c.nsets * (h->nplans ? h->nplans : 1) + 1;      // (a multi-plan handle sorts by (set, plan) pair)
+    const int nb = h->c.nsets * h->plans() + 1;      // (a multi-plan handle sorts by (set, plan) pair)
     if (batch + nb > h->order_cap) {
         HIP_TRY(hipDeviceSynchronize());                       // (a set-up call: launches that still read the old order finish first)
         h->order_batch = 0;
@@ -699,7 +688,7 @@ int ismpc_sweep_verify_tables(ismpc_handle* h, int set, double* rel_err)
     int rc = ismpc::build_tables(h->sets[set], h->ftsp.data(), h->t.rows, t, err);
     if (rc != ISMPC_OK) return fail(rc, err);
     const ismpc::SweepSlabs& S = h->sw;
-    const int N = t.p.N, NG = S.NG, NTq = ismpc::Tables::NT;
+    const int N = t.p.N, NG = S.NG;
     auto fetch = [&](const double* src, size_t n, std::vector<double>& dst) -> bool { dst.resize(n); return hipMemcpy(dst.data(), src, n * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess; };
     auto rel = [](const std::vector<double>& d, const std::vector<double>& hst) { double e = 0, m = 0; for (size_t i = 0; i < hst.size(); ++i) { e = std::max(e, std::fabs(d[i] - hst[i])); m = std::max(m, std::fabs(hst[i])); } return m > 0 ? e / m : e; };
     std::vector<double> d, hv;
@@ -715,17 +704,14 @@ int ismpc_sweep_verify_tables(ismpc_handle* h, int set, double* rel_err)
     rel_err[4] = rel(d, t.HSt);
     if (!fetch(S.SHSt + (size_t)set * S.s_HS, S.s_HS, d)) return fail(ISMPC_E_NO_DEVICE, "download failed");
     rel_err[5] = rel(d, t.SHSt);
-    { std::vector<double> dx, dy; const size_t ts = (size_t)set * (h->nplans ? h->nplans : 1) * S.s_tail;      // (a multi-plan handle: the tails of (set, plan 0))
+    { std::vector<double> dx, dy; const size_t ts = (size_t)set * h->plans() * S.s_tail;      // (a multi-plan handle: the tails of (set, plan 0))
       if (!fetch(S.tailx + ts, S.s_tail, dx) || !fetch(S.taily + ts, S.s_tail, dy)) return fail(ISMPC_E_NO_DEVICE, "download failed");
       rel_err[6] = std::max(rel(dx, t.tailx), rel(dy, t.taily)); }
     rel_err[7] = 0.0;
     for (int pass = 0; pass < (S.vqT2 ? 2 : 1); ++pass) {   // the lane-group layouts (16 lanes, 8 lanes), against the host's re-striding of ITS vtab
-        const int lpi = pass == 0 ? 16 : 8, R = quad_R(N, lpi); const size_t npp = (size_t)t.npat + 1;
-        hv.assign(npp * R * 3 * lpi * 2, 0.0);
-        for (size_t pp = 0; pp < npp; ++pp) for (int r = 0; r < R; ++r) for (int k = 0; k < 3; ++k) for (int li = 0; li < lpi; ++li) {
-            const int n = li * R + r; const size_t dst = (((pp * R + r) * 3 + k) * lpi + li) * 2;
-            hv[dst] = t.vtab[(pp * 6 + 2 * k) * NTq + n]; hv[dst + 1] = t.vtab[(pp * 6 + 2 * k + 1) * NTq + n];
-        }
+        const int lpi = pass == 0 ? 16 : 8;
+        std::vector<double> tzgT;
+        ismpc::lane_group_tables(t, lpi, quad_R(N, lpi), hv, tzgT);
         if (!fetch(pass == 0 ? S.vqT + (size_t)set * S.s_vqT : S.vqT2 + (size_t)set * S.s_vqT2, pass == 0 ? S.s_vqT : S.s_vqT2, d)) return fail(ISMPC_E_NO_DEVICE, "download failed");
         rel_err[7] = std::max(rel_err[7], rel(d, hv));
     }
@@ -849,45 +835,26 @@ int ismpc_rollout_device(ismpc_handle* h, int batch, ismpc_tick_in* state_dev, i
     if (h->timing) HIP_TRY(hipEventRecord(h->ev0, s));
     if (batch > 0 && ticks > 0 && h->kernel_rollout && !h->dense_path && h->quad_path && h->c.N <= 128 && h->z_fallback) {
         // the whole closed loop in ONE launch: state in registers, one trajectory record per tick (ismpc_rollout_quad)
-        const LaneLayout lay = pick_layout(h, batch, false);
-        const int lpi = lay.lpi;
-        DevConst cq = h->c;
-        cq.vqT = lay.vqT; cq.tzgT = lay.tzgT;
-        const int waves = (batch * lpi + 63) / 64;
-        const dim3 qgrid((waves + ISMPC_QUAD_WAVES - 1) / ISMPC_QUAD_WAVES), qblock(64 * ISMPC_QUAD_WAVES);
+        const QuadLaunch q = quad_launch(h, batch, false);
         if (batch > h->zstop_cap)                         // stream-ordered growth, as zmark (ismpc_reserve sizes it beforehand)
             ISMPC_GROW_ASYNC(fail, h, h->zstop, h->zstop_cap, batch, sizeof(int) * (size_t)batch, s);
         const int lid = ++h->launch_id;
         const dim3 rgrid(std::min((batch + ISMPC_QUAD_WAVES - 1) / ISMPC_QUAD_WAVES, 64));
-        // the rollout itself, then its resume launch (FB = true)
-        auto roll = [&](auto first, auto resume) {
-            hipLaunchKernelGGL(first, qgrid, qblock, 0, s, cq, state_dev, traj_dev, batch, first_frame, ticks, h->zstop, lid);
-            hipLaunchKernelGGL(resume, rgrid, qblock, 0, s, cq, state_dev, traj_dev, batch, first_frame, ticks, h->zstop, lid);
-        };
-        auto note = [&](int lanes, int r, int rw) {          // (ismpc_last_launch_info: the rollout and its resume launch)
-            const int v[8] = {ISMPC_KERNEL_ROLLOUT_QUAD, lanes, r, rw, (h->sweep ? 1 : 0) | (h->nplans ? 2 : 0), 2, batch, 0};
-            std::memcpy(h->last_launch, v, sizeof(v));
-        };
-        // (a sweep handle rolls out at 16 lanes per instance: the SW kernels are instantiated for that shape only)
-        if (h->sweep && lpi != 16) return fail(ISMPC_E_UNSUPPORTED, "parameter sweep: rollouts take 16 lanes per instance");
-        if (h->nplans) {
-            cq.sets = (lpi == 8 && h->sets8) ? h->sets8 : ((lpi == 32 && h->sets32) ? h->sets32 : h->c.sets);
-            quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
-                roll(ismpc_rollout_quad<RR, LL, RW_, false, 2>, ismpc_rollout_quad<RR, LL, RW_, true, 2>);
-                note(LL, RR, RW_);
+        const int rc = with_sw(h, [&](auto SW) {
+            constexpr int sw = decltype(SW)::value;
+            return quad_shape(h->c.N, q.lpi, [&](auto RR, auto LL, auto RW_) {
+                if constexpr (has_rollout_quad(LL, sw)) {
+                    // the rollout itself, then its resume launch (FB = true)
+                    hipLaunchKernelGGL((ismpc_rollout_quad<RR, LL, RW_, false, sw>), q.grid, q.block, 0, s, q.c, state_dev, traj_dev, batch, first_frame, ticks, h->zstop, lid);
+                    hipLaunchKernelGGL((ismpc_rollout_quad<RR, LL, RW_, true, sw>), rgrid, q.block, 0, s, q.c, state_dev, traj_dev, batch, first_frame, ticks, h->zstop, lid);
+                    const int v[8] = {ISMPC_KERNEL_ROLLOUT_QUAD, LL, RR, RW_, form_bits(h), 2, batch, 0};      // (ismpc_last_launch_info: the rollout and its resume launch)
+                    std::memcpy(h->last_launch, v, sizeof(v));
+                    return ISMPC_OK;
+                } else      // (a sweep handle rolls out at 16 lanes per instance: the SW = 1 kernels are instantiated for that shape only)
+                    return fail(ISMPC_E_UNSUPPORTED, "parameter sweep: rollouts take 16 lanes per instance");
             });
-        } else if (h->sweep)
-            quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
-                if constexpr (LL == 16) {
-                    roll(ismpc_rollout_quad<RR, 16, RW_, false, 1>, ismpc_rollout_quad<RR, 16, RW_, true, 1>);
-                    note(16, RR, RW_);
-                }
-            });
-        else
-            quad_shape(h->c.N, lpi, [&](auto RR, auto LL, auto RW_) {
-                roll(ismpc_rollout_quad<RR, LL, RW_, false>, ismpc_rollout_quad<RR, LL, RW_, true>);
-                note(LL, RR, RW_);
-            });
+        });
+        if (rc != ISMPC_OK) return rc;
         HIP_TRY(hipGetLastError());
     } else {
         for (int t = 0; t < ticks; ++t) {

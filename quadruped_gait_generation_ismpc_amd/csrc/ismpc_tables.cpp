@@ -253,4 +253,21 @@ int build_tables(const ismpc_params& p, const double* ftsp, int rows, Tables& t,
     return ISMPC_OK;
 }
 
+void lane_group_tables(const Tables& t, int lpi, int R, std::vector<double>& vqT, std::vector<double>& tzgT)
+{
+    constexpr int NT = Tables::NT;
+    const size_t npp = (size_t)t.npat + 1;
+    vqT.assign(npp * R * 3 * lpi * 2, 0.0); tzgT.assign((size_t)R * lpi * 2, 0.0);
+    for (size_t pp = 0; pp < npp; ++pp)
+        for (int r = 0; r < R; ++r)
+            for (int k = 0; k < 3; ++k)
+                for (int li = 0; li < lpi; ++li) {
+                    const int n = li * R + r;                       // < lpi * R <= NT
+                    const size_t dst = (((pp * R + r) * 3 + k) * lpi + li) * 2;
+                    vqT[dst] = t.vtab[(pp * 6 + 2 * k) * NT + n]; vqT[dst + 1] = t.vtab[(pp * 6 + 2 * k + 1) * NT + n];
+                }
+    for (int r = 0; r < R; ++r)
+        for (int li = 0; li < lpi; ++li) { const int n = li * R + r; tzgT[((size_t)r * lpi + li) * 2] = t.tz[n]; tzgT[((size_t)r * lpi + li) * 2 + 1] = t.tg[n]; }
+}
+
 }  // namespace ismpc

@@ -53,4 +53,10 @@ void build_plan_tables(const ismpc_params& p, const double* ftsp, int rows, Plan
 // Returns ISMPC_OK or an ISMPC_E_* code; on error `err` explains.
 int build_tables(const ismpc_params& p, const double* ftsp, int rows, Tables& out, std::string& err);
 
+// The affine tables as the lane-group kernels read them, lane-contiguous, at lpi lanes per instance and R samples per lane
+// (lpi * R <= Tables::NT): lane li holds the samples li*R .. li*R + R - 1.
+//   vqT[(((p*R + r)*3 + k)*lpi + li)*2 + j] = vtab[(p*6 + 2*k + j)*NT + li*R + r]      every pattern p, npat ("no equalities") included
+//   tzgT[(r*lpi + li)*2 + {0, 1}]           = {tz, tg}[li*R + r]
+void lane_group_tables(const Tables& t, int lpi, int R, std::vector<double>& vqT, std::vector<double>& tzgT);
+
 }  // namespace ismpc

@@ -47,4 +47,21 @@ void probe_hinv(void* h, double* dst) { auto* t = static_cast<ismpc::Tables*>(h)
 int probe_np(void* h) { return static_cast<ismpc::Tables*>(h)->NP; }
 void probe_tail(void* h, int idx, double* tx, double* ty) { auto* t = static_cast<ismpc::Tables*>(h); *tx = t->tailx[idx]; *ty = t->taily[idx]; }
 
+// the affine tables as built: vtab (npat + 1) x 6 x NT, tz and tg NT each
+void probe_affine(void* h, double* vtab, double* tz, double* tg)
+{
+    auto* t = static_cast<ismpc::Tables*>(h);
+    std::memcpy(vtab, t->vtab.data(), sizeof(double) * t->vtab.size());
+    std::memcpy(tz, t->tz.data(), sizeof(double) * t->tz.size()); std::memcpy(tg, t->tg.data(), sizeof(double) * t->tg.size());
+}
+// ... and in the lane-group layout (csrc/ismpc_tables.cpp lane_group_tables): the sizes, and the tables where a destination is given
+void probe_lane_group(void* h, int lpi, int R, double* vqT, double* tzgT, long long* n_vqT, long long* n_tzgT)
+{
+    std::vector<double> a, b;
+    ismpc::lane_group_tables(*static_cast<ismpc::Tables*>(h), lpi, R, a, b);
+    *n_vqT = (long long)a.size(); *n_tzgT = (long long)b.size();
+    if (vqT) std::memcpy(vqT, a.data(), sizeof(double) * a.size());
+    if (tzgT) std::memcpy(tzgT, b.data(), sizeof(double) * b.size());
+}
+
 }

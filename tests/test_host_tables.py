@@ -1,6 +1,6 @@
 """CPU-only: the host precompute of the HIP path (csrc/ismpc_tables.cpp) against the oracle --
-inverse of the vertical Hessian, equality patterns, and the affine form of the vertical stage
-(flat plan and a staircase plan), without a GPU."""
+inverse of the vertical Hessian, equality patterns, the affine form of the vertical stage
+(flat plan and a staircase plan) and its lane-group layout, without a GPU."""
 import ctypes as C
 import os
 import subprocess
@@ -33,6 +33,8 @@ def probe():
     lib.probe_vertical.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.probe_hinv.argtypes = [C.c_void_p, C.c_void_p]
     lib.probe_tail.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.probe_affine.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.probe_lane_group.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     return lib
 
 
@@ -127,4 +129,29 @@ def test_tail_table(probe, built_libs):
         probe.probe_tail(h, idx, C.byref(tx), C.byref(ty))
         assert abs(tx.value - eta * p.mpc_dt * d @ mid[idx + N: idx + 2 * N, 0]) < 1e-12
         assert abs(ty.value - eta * p.mpc_dt * d @ mid[idx + N: idx + 2 * N, 1]) < 1e-12
+    probe.probe_free(h)
+
+
+@pytest.mark.parametrize("N,lpi,R", [(37, 8, 8), (100, 8, 13), (100, 16, 7), (100, 32, 4), (128, 8, 16)])
+def test_lane_group_layout_is_the_affine_tables_restrided(probe, N, lpi, R, built_libs):
+    """lane_group_tables(): lane li of a group holds the samples li*R .. li*R + R - 1, element for element out of vtab / tz / tg.
+    The shapes are those of tests/test_gpu_dispatch_parity.py at which li*R + r runs past N (into the zero padding of vtab) or reaches
+    the largest sample index, 127."""
+    NT = 256
+    h = build(probe, O.default_params(N), O.reference_plan())
+    npp = probe.probe_npat(h) + 1                    # every equality pattern and "no equalities"
+    vtab = np.zeros((npp, 6, NT)); tz = np.zeros(NT); tg = np.zeros(NT)
+    probe.probe_affine(h, vtab.ctypes.data_as(C.c_void_p), tz.ctypes.data_as(C.c_void_p), tg.ctypes.data_as(C.c_void_p))
+    nv, nt = C.c_longlong(), C.c_longlong()
+    probe.probe_lane_group(h, lpi, R, None, None, C.byref(nv), C.byref(nt))
+    assert (nv.value, nt.value) == (npp * R * 3 * lpi * 2, R * lpi * 2)
+    vqT = np.full((npp, R, 3, lpi, 2), np.nan); tzgT = np.full((R, lpi, 2), np.nan)
+    probe.probe_lane_group(h, lpi, R, vqT.ctypes.data_as(C.c_void_p), tzgT.ctypes.data_as(C.c_void_p), C.byref(nv), C.byref(nt))
+    n = np.arange(lpi)[None, :] * R + np.arange(R)[:, None]          # n[r, li] = li*R + r
+    assert n.max() < NT and vtab.any() and np.all(vtab[:, :, N:] == 0)
+    for p in range(npp):
+        for k in range(3):
+            for j in range(2):
+                assert np.array_equal(vqT[p, :, k, :, j], vtab[p, 2 * k + j][n]), (p, k, j)
+    assert np.array_equal(tzgT[:, :, 0], tz[n]) and np.array_equal(tzgT[:, :, 1], tg[n])
     probe.probe_free(h)
