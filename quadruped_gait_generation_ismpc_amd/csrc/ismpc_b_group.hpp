@@ -177,9 +177,14 @@ template <int R, int LPI> constexpr int wave_lds_double2_fb() { return wave_lds_
 // (per-lane loads); horizon, plan, dt, g and the gate are the handle's.  SW = 0 compiles to exactly the plain kernel.
 // SW = 2: multi-plan handle -- the record is the one of the instance's (set, plan) pair, and the plan is read through it too: the
 // midpoint window (the same coalesced load from another base address), the tails and, in the callers, the step timings.
-template <int R, int LPI, int KF, int SW = 0>
+// `keep` (group-uniform): will anything of this group be stored?  A tail group, whose record nobody reads, never enters the knapsack
+// loop.  MF: a group in flight or gated does not enter it either.  That is the per-tick kernels; the rollout passes MF = false,
+// which masks nothing (keep is not read) and compiles to the loop it always had: it sets one simulation time for its whole batch, so its
+// wavefronts hold one gait phase, and both a flight test and a parking mask (valid && alive) measured slower there
+// (scripts/bench_rollout.py, -1 to -3 %).
+template <int R, int LPI, int KF, int SW = 0, bool MF = true>
 __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lane, const QState& s, QOut& o, double* __restrict__ u_traj_inst,
-                                                double2* __restrict__ lds_wave)
+                                                double2* __restrict__ lds_wave, const bool keep)
 {
     constexpr int NT = ismpc::Tables::NT;
     const int N = c.N;
@@ -353,7 +358,13 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
     const double iq0 = frcp(q0);
     double tau[2] = { Tq[0] * iq0, Tq[1] * iq0 };
     int its[2] = {1, 1}, prev[2] = {0, 0};
-    bool live[2] = {true, true};
+    // Nothing of stage 3 survives for a group in flight (lam0 <= gate, MPCSolver.cpp:322; a NaN lam0 is flight, as in the integration
+    // below) or a gated one: ux0, uy0, itx, ity stay 0, st3 is not merged, the u_traj rows of x and y are 0.  Such a group is never
+    // live, so it does not keep the other groups of its wavefront in the loop.  (A deferred group stays live: its provisional record
+    // is observable in the two-launch form and with ISMPC_Z_FALLBACK=0.)  A group that is not live keeps tau at its start; its
+    // ux0 / uy0 are then not the converged ones, and none of it is stored (every store of a tail group is guarded by `valid`).
+    const bool stage3 = run && Grp<LPI>::bcast0(lam0_l) > c.gate;
+    bool live[2] = {MF ? keep && stage3 : true, MF ? keep && stage3 : true};
     int st3 = 0;
     if (!(q0 > 0.0)) {                                                       // no sample can move the ZMP
 #pragma unroll
@@ -368,7 +379,7 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
 #pragma unroll
             for (int ax = 0; ax < 2; ++ax) {
                 if (__builtin_amdgcn_ballot_w64(live[ax]) == 0ull) continue;      // this axis is done in every group of the wavefront (the other one
-                                                                                  // keeps the loop alive for 0.6 more rounds on average: scripts/knapsack_hist.py)
+                                                                                  // may keep the loop alive: scripts/knapsack_model.py)
                 int cl = 0;
 #pragma unroll
                 for (int r = 0; r < R; ++r) cl += (tau[ax] * fabs(a[r]) >= h) ? 1 : 0;
@@ -461,7 +472,6 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
     }
     o.status = status;
     if (u_traj_inst) {
-        const bool stage3 = run && Grp<LPI>::bcast0(lam0_l) > c.gate;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int n = n0 + r;
@@ -505,7 +515,7 @@ __device__ __forceinline__ bool tick_group_body(const DevConst& c, const int gi_
         if (SW) { const int ps = rec->reserved; s.ps = (ps >= 0 && ps < c.nsets) ? ps : -1; }   // an unknown set: ISMPC_ST_BAD_INDEX, state passed through
     }
     QOut o;
-    const bool deferred = tick_group_core<R, LPI, KF, SW>(c, lane, s, o, (u_traj && valid) ? u_traj + (size_t)gi * 3 * c.N : nullptr, lds_wave);
+    const bool deferred = tick_group_core<R, LPI, KF, SW>(c, lane, s, o, (u_traj && valid) ? u_traj + (size_t)gi * 3 * c.N : nullptr, lds_wave, valid);
     if ((lane & (LPI - 1)) == 0 && valid) {
         if (out) store_record(out + gi, o);
         if (deferred) {
@@ -655,7 +665,7 @@ void ismpc_rollout_quad(const DevConst c, ismpc_tick_in* state, ismpc_tick_out* 
             if (s.w.fc >= 0 && s.w.fc < c.rows && s.w.sim >= ftsp_t[s.w.fc] - 1) { s.w.ctl = 0; s.w.mpc = 0; s.w.fc = s.w.fc + 1; }
             s.w.sim = (double)frame;
             QOut o;
-            const bool def = tick_group_core<R, LPI, ISMPC_KF_ROLLOUT, SW>(c, lane, s, o, nullptr, lds_mid[wv]);
+            const bool def = tick_group_core<R, LPI, ISMPC_KF_ROLLOUT, SW, false>(c, lane, s, o, nullptr, lds_mid[wv], true);      // (no mask here: see tick_group_core)
             const bool park = def && alive;
             if (li == 0 && valid && alive && !def && traj) store_record(traj + (size_t)t * batch + gi, o);
             // a deferred instance: its pre-tick state goes to memory (FB = false: to stay there; FB = true: for the fallback body)

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Diagnostic: Newton iterations of the two horizontal knapsack solves per instance on the headline batch, and the per-wavefront maximum
-(four instances per wavefront iterate in lockstep).  GPU box."""
+(the instances of a wavefront iterate in lockstep; how many there are is read from the layout the launch dispatched).  GPU box.
+The records hold nothing of stage 3 for a flight or a gated instance: their `iters` is 0, whatever their QPs would have taken.  Since the
+flight mask of tick_group_core that is also what the kernel iterates for; what the loop cost before, flight QPs included, is modelled on
+the CPU by scripts/knapsack_model.py."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -11,14 +14,17 @@ p = q.default_params(N=100)
 s = q.MPCSolver(q.reference_plan(params=p), params=p)
 tin = workload.make_batch(100, B)
 out = s.solve_batch(tin)
+info = s.launch_info()
+IPW = 64 // info["lanes"]                          # instances per wavefront of the kernel that ran
+print(f"{info['family']}: {info['lanes']} lanes per instance, R = {info['R']}, {IPW} instances per wavefront")
 st = out["status"]
 run = (st & (q.ST_FLIGHT | q.ST_BAD_INDEX | q.ST_TICK_SKIPPED)) == 0
 itx, ity = out["iters"] & 255, (out["iters"] >> 8) & 255
 it = np.where(run, np.maximum(itx, ity), 0)
-print("instances in stage 3:", run.mean())
+print("instances in stage 3:", run.mean(), "(the others -- flight, gated -- report 0 iterations and are counted as 0 below)")
 for name, v in (("x", itx[run]), ("y", ity[run]), ("max(x,y)", it[run])):
     print(name, "hist 1..8+:", [int((v == k).sum()) for k in range(1, 8)], int((v >= 8).sum()), "mean %.2f" % v.mean())
-w = it.reshape(-1, 4).max(1)                       # per wavefront (4 instances)
+w = it.reshape(-1, IPW).max(1)                     # per wavefront
 print("per-wavefront max hist 0..8+:", [int((w == k).sum()) for k in range(0, 8)], int((w >= 8).sum()), "mean %.2f" % w.mean())
-wx = np.where(run, itx, 0).reshape(-1, 4).max(1); wy = np.where(run, ity, 0).reshape(-1, 4).max(1)
+wx = np.where(run, itx, 0).reshape(-1, IPW).max(1); wy = np.where(run, ity, 0).reshape(-1, IPW).max(1)
 print("per-wavefront per-axis max: x mean %.2f y mean %.2f; sum of per-axis iterations per wavefront mean %.2f" % (wx.mean(), wy.mean(), (wx + wy).mean()))

@@ -1,0 +1,114 @@
+#!/usr/bin/env python3
+"""CPU model of the knapsack Newton loop of the lane-group tick core (csrc/ismpc_b_group.hpp, KF = 0 schedule): how many count and sum
+passes a wavefront runs per axis when its groups iterate in lockstep, with and without the flight / gate mask on `live`.  No GPU.
+
+The sample is workload.make_batch(100, B).  The oracle's `gi` backend gives the vertical trajectory (want_traj); lambda_j is rebuilt from
+it (MPCSolver.cpp:306), a_n comes from the backward walk (:353-384), and the kernel's own Newton rule is replayed per QP -- for flight
+instances too, whose records say 0 iterations because nothing of stage 3 is stored (scripts/knapsack_hist.py cannot see them).
+Instructions per pass are read off the source, not off the ISA: count = 3 R + 2 log2(lanes), sum = 7 R + 6 log2(lanes) + 1
+(R = 13, 8 lanes: 45 and 110).
+
+usage: python scripts/knapsack_model.py [instances = 4096] [lanes per instance = 8]"""
+import math, os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+from oracle import oracle as O
+from quadruped_gait_generation_ismpc_amd import workload
+
+B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
+LPI = int(sys.argv[2]) if len(sys.argv) > 2 else 8
+N = 100
+assert LPI in (8, 16, 32)
+IPW, R = 64 // LPI, {8: 13, 16: 7, 32: 4}[LPI]                      # the instantiated shape at N = 100 (quad_shape of csrc/ismpc_hip.hip)
+p = O.default_params(N)
+orc = O.Oracle(p, backend="gi")
+tin = workload.make_batch(N, B)
+ref, info, traj = orc.solve(tin, want_traj=True)
+run = (ref["status"] & (O.ST_BAD_INDEX | O.ST_TICK_SKIPPED)) == 0
+dt, m, g, gate, eta = p.mpc_dt, p.mass, p.g, p.lambda_gate, math.sqrt(p.g / p.h_des)
+
+# ---- lambda_j from the vertical trajectory: z_j = z0 + (j+1) dt zd0 + sum_{k<j} (j-k) dt^2/m u_k - g dt^2 j (j+1) / 2
+uz = traj[:, 0, :]
+j = np.arange(N)
+Sz = np.where(j[:, None] > j[None, :], (j[:, None] - j[None, :]) * dt * dt / m, 0.0)
+zpos = uz @ Sz.T + tin["com_pos"][:, 2:3] + (j + 1) * dt * tin["com_vel"][:, 2:3] - g * dt * dt * j * (j + 1) / 2
+lam = (uz / m) / zpos
+stage3 = run & (lam[:, 0] > gate)
+seen = run & ((ref["status"] & O.ST_FLIGHT) == 0)
+d0 = np.abs(lam[seen, 0] - info["lambda0"][seen]) / np.abs(info["lambda0"][seen])
+print(f"{B} instances, {LPI} lanes per instance (R = {R}, {IPW} instances per wavefront)")
+print(f"lambda_0 against the oracle's: max rel {d0.max():.1e}; flight fraction {(run & ~stage3).mean():.3f} (oracle: {((ref['status'] & O.ST_FLIGHT) != 0).mean():.3f})")
+
+# ---- a_n = C_sc A_{N-1} ... A_{n+1} B_n (backward walk), beq - a'mid
+le = np.where(lam < gate, 0.0, lam)
+x = np.sqrt(le) * dt
+ch1 = np.cosh(x) - 1.0
+s1 = np.where(x > 0, dt * np.sinh(x) / np.where(x > 0, x, 1.0), dt)
+s2 = le * s1
+c0, c1 = np.ones(B), np.full(B, 1.0 / eta)
+a = np.zeros((B, N))
+for n in range(N - 1, -1, -1):
+    a[:, n] = -(c0 * ch1[:, n] + c1 * s2[:, n])
+    c0, c1 = c0 * (1.0 + ch1[:, n]) + c1 * s2[:, n], c0 * s1[:, n] + c1 * (1.0 + ch1[:, n])
+mid = orc.midpoint()
+idx = np.where(run, info["idx"], 0)
+win = idx[:, None] + j[None, :]
+deltas = eta * dt * np.exp(-dt * eta * j)
+h = np.where(tin["footstep_counter"] > 1, p.foot_width / 2, p.first_step_halfwidth)
+Tq = np.zeros((B, 2))
+for ax in range(2):
+    tail = (deltas[None, :] * mid[win + N, ax]).sum(1)
+    beq = tail - (c0 * tin["com_pos"][:, ax] + c1 * tin["com_vel"][:, ax])
+    if ax == 0:
+        db = np.abs(beq[stage3] - info["beq"][stage3, 0]) / np.maximum(np.abs(info["beq"][stage3, 0]), 1e-6)
+        print(f"beq_x against the oracle's on the stage-3 instances: max rel {db.max():.1e}")
+    Tq[:, ax] = np.abs(beq - (a * mid[win, ax]).sum(1))
+
+# ---- the kernel's Newton rule per QP: (count passes, sum passes)
+ab = np.abs(a)
+q0 = (a * a).sum(1)
+cnt_p, sum_p = np.zeros((B, 2), int), np.zeros((B, 2), int)
+for ax in range(2):
+    tau = Tq[:, ax] / q0
+    live = np.ones(B, bool)
+    prev = np.zeros(B, int)
+    for it in range(N + 2):
+        if not live.any():
+            break
+        sat = tau[:, None] * ab >= h[:, None]
+        cnt = sat.sum(1)
+        cnt_p[live, ax] += 1
+        live &= cnt != prev
+        sum_p[live, ax] += 1
+        ssat, qfree = (ab * sat).sum(1), (a * a * ~sat).sum(1)
+        tn = (Tq[:, ax] - h * ssat) / np.where(qfree > 0, qfree, 1.0)
+        stop = live & (~(qfree > 0) | ~(tn > tau))
+        go = live & ~stop
+        tau = np.where(go, tn, tau); prev = np.where(go, cnt, prev)
+        live = go
+
+
+def hist(v, top=8):
+    return [int((v == k).sum()) for k in range(top)] + [int((v >= top).sum())]
+
+
+fl = run & ~stage3
+print(f"flight QPs ({2 * int(fl.sum())}): sum passes 0..7, 8+: {hist(sum_p[fl].ravel())}; count passes: {hist(cnt_p[fl].ravel())}")
+print(f"stage-3 QPs ({2 * int(stage3.sum())}): sum passes 0..7, 8+: {hist(sum_p[stage3].ravel())}; count passes: {hist(cnt_p[stage3].ravel())}")
+print(f"stage-3 QPs that need no update: {(sum_p[stage3] == 0).mean():.3f}")
+
+# ---- lockstep: a wavefront runs the count pass of an axis while one of its groups is live on it, the sum pass while one is live after it
+W = B // IPW
+c_cnt, c_sum = 3 * R + 2 * int(math.log2(LPI)), 7 * R + 6 * int(math.log2(LPI)) + 1
+print(f"instructions per pass (from the source): count {c_cnt}, sum {c_sum}")
+print("| | count passes | sum passes | VALU instr. in the loop per wavefront |\n|---|---|---|---|")
+res = {}
+for name, mask in (("without the mask", np.ones(B, bool)), ("with the mask", stage3)):
+    cp = np.where(mask[:, None], cnt_p, 0)[:W * IPW].reshape(W, IPW, 2).max(1)
+    sp = np.where(mask[:, None], sum_p, 0)[:W * IPW].reshape(W, IPW, 2).max(1)
+    instr = (cp * c_cnt + sp * c_sum).sum(1).mean()
+    res[name] = instr
+    print(f"| {name} | {cp.mean():.2f} | {sp.mean():.2f} | {instr:.0f} |")
+vals = list(res.values())
+print(f"difference: {vals[0] - vals[1]:.0f} VALU instructions per wavefront")
