@@ -149,7 +149,7 @@ __device__ int z_active_set(const DevConst& c, int lane, int n0, int pat, double
     const int N = c.N, cap = c.zcap;
     int elo = 0, ne = 0;
     if (pat < c.npat) { elo = c.e_lo[pat]; ne = c.ne[pat]; }
-    const double tol_lo = 1e-11 * fmax(1.0, fabs(c.z_lo)), tol_hi = 1e-11 * fmax(1.0, fabs(c.z_hi));
+    const double tol_lo = z_tol(c.z_lo), tol_hi = z_tol(c.z_hi);
     ZStore z; z.bind(lds, c.zldsq);
     int slot = -1;
     bool sact[R];
@@ -368,7 +368,7 @@ __device__ __forceinline__ void tick_affine_body(const DevConst& c, const int gi
         }
         bool viol = false;
         double lam[R];
-        const double zlo_t = c.z_lo - 1e-11 * fmax(1.0, fabs(c.z_lo)), zhi_t = c.z_hi + 1e-11 * fmax(1.0, fabs(c.z_hi));
+        const double zlo_t = c.z_lo - z_tol(c.z_lo), zhi_t = c.z_hi + z_tol(c.z_hi);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int n = n0 + r;
@@ -387,10 +387,7 @@ __device__ __forceinline__ void tick_affine_body(const DevConst& c, const int gi
             lam[r] = (c.g + zacc) * frcp(zpos);                                 // MPCSolver.cpp:306
         }
         uz0 = bcast0(u[0]);
-        o_z = fma(dt, zd0, z0);                                                 // MPCSolver.cpp:274-278
-        o_zd = fma(c.dt_over_mass, uz0, zd0) - dt * c.g;
-        if (isnan(o_z)) { o_z = c.h_des; status |= ISMPC_ST_Z_NAN; }
-        if (isnan(o_zd)) { o_zd = 0.0; status |= ISMPC_ST_Z_NAN; }
+        integrate_z(c, c.dt_over_mass, c.h_des, z0, zd0, uz0, o_z, o_zd, status);
 
         // ---- A_j, B_j (MPCSolver.cpp:353-361): A = [1+wQ, dt P; lam dt P, 1+wQ], B = [-wQ, -lam dt P]
         double ch1[R], s1[R], s2[R];
@@ -405,42 +402,26 @@ __device__ __forceinline__ void tick_affine_body(const DevConst& c, const int gi
             big = big || (wv_[r] > 0.25);
             mid = mid || (wv_[r] > 0.004);
         }
-        // w = lambda dt^2 is <= 0.0025 on a physical gait (lambda <= 25 at dt = 0.01): degree 3 in w is then exact to
-        // < 1 ulp (next term w^4/9! <= 7e-16 relative to 1 at w = 0.004); the wave takes degree 7 only if some lane needs it
+        // degree 3 where every lane's w allows it (taylor_low); the wave takes degree 7 only if some lane needs it
         if (__builtin_amdgcn_ballot_w64(mid) == 0) {
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const double wv = wv_[r];
-                double P = 1.0 / 5040.0, Q = 1.0 / 40320.0;
-                P = fma(P, wv, 1.0 / 120.0);         Q = fma(Q, wv, 1.0 / 720.0);
-                P = fma(P, wv, 1.0 / 6.0);           Q = fma(Q, wv, 1.0 / 24.0);
-                P = fma(P, wv, 1.0);                 Q = fma(Q, wv, 0.5);
-                ch1[r] = wv * Q; s1[r] = dtn_[r] * P; s2[r] = le_[r] * s1[r];
+                double P = TAYLOR_P3, Q = TAYLOR_Q3;
+                taylor_low(wv_[r], P, Q);
+                ab_series(wv_[r], dtn_[r], le_[r], P, Q, ch1[r], s1[r], s2[r]);
             }
         } else {
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const double wv = wv_[r];
-                double P = 1.0 / 1307674368000.0, Q = 1.0 / 20922789888000.0;
-                P = fma(P, wv, 1.0 / 6227020800.0);  Q = fma(Q, wv, 1.0 / 87178291200.0);
-                P = fma(P, wv, 1.0 / 39916800.0);    Q = fma(Q, wv, 1.0 / 479001600.0);
-                P = fma(P, wv, 1.0 / 362880.0);      Q = fma(Q, wv, 1.0 / 3628800.0);
-                P = fma(P, wv, 1.0 / 5040.0);        Q = fma(Q, wv, 1.0 / 40320.0);
-                P = fma(P, wv, 1.0 / 120.0);         Q = fma(Q, wv, 1.0 / 720.0);
-                P = fma(P, wv, 1.0 / 6.0);           Q = fma(Q, wv, 1.0 / 24.0);
-                P = fma(P, wv, 1.0);                 Q = fma(Q, wv, 0.5);
-                ch1[r] = wv * Q; s1[r] = dtn_[r] * P; s2[r] = le_[r] * s1[r];
+                double P, Q;
+                taylor_high(wv_[r], P, Q); taylor_low(wv_[r], P, Q);
+                ab_series(wv_[r], dtn_[r], le_[r], P, Q, ch1[r], s1[r], s2[r]);
             }
         }
         if (__builtin_amdgcn_ballot_w64(big) != 0) {      // lambda dt^2 > 1/4: off any physical gait; libm, wave-uniform
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int n = n0 + r;
-                const double le = (lam[r] < c.gate) ? 0.0 : lam[r];
-                const double dtn = (n < N) ? dt : 0.0;
-                const double wv = le * dtn * dtn;
-                if (wv > 0.25) { const double x = sqrt(wv); ch1[r] = cosh(x) - 1.0; s1[r] = dtn * (sinh(x) / x); s2[r] = le * s1[r]; }
-            }
+            for (int r = 0; r < R; ++r)
+                if (wv_[r] > 0.25) ab_libm(wv_[r], dtn_[r], le_[r], ch1[r], s1[r], s2[r]);
         }
         const double lam0 = bcast0(lam[0]);
         const double A0a = 1.0 + bcast0(ch1[0]), A0b = bcast0(s1[0]), A0c = bcast0(s2[0]);
@@ -526,34 +507,20 @@ __device__ __forceinline__ void tick_affine_body(const DevConst& c, const int gi
             }
             tau0 = tau[0]; tau1 = tau[1]; itx = its[0]; ity = its[1];
             {   // first decision variables (lane 0 holds sample 0)
-                const double a0 = bcast0(a[0]), aa0 = fabs(a0), sa0 = (a0 < 0.0) ? -1.0 : 1.0;
-                const double m0x = bcast0(mx[0]), m0y = bcast0(my[0]);
-                ux0 = fma(sgx * sa0, (aa0 > 0.0) ? fmin(tau0 * aa0, h) : 0.0, m0x);
-                uy0 = fma(sgy * sa0, (aa0 > 0.0) ? fmin(tau1 * aa0, h) : 0.0, m0y);
+                const double a0 = bcast0(a[0]);
+                ux0 = box_move(sgx, a0, tau0, h, bcast0(mx[0]));
+                uy0 = box_move(sgy, a0, tau1, h, bcast0(my[0]));
             }
         } else {
             status |= ISMPC_ST_FLIGHT;
         }
         // ---- integration with A(lambda_0), B(lambda_0), MPCSolver.cpp:406-422
-        o_x  = fma(1.0 - A0a, ux0, fma(A0a, x0, A0b * xd0));
-        o_xd = fma(-A0c, ux0, fma(A0c, x0, A0a * xd0));
-        o_y  = fma(1.0 - A0a, uy0, fma(A0a, y0, A0b * yd0));
-        o_yd = fma(-A0c, uy0, fma(A0c, y0, A0a * yd0));
+        integrate_xy(A0a, A0b, A0c, x0, xd0, ux0, o_x, o_xd);
+        integrate_xy(A0a, A0b, A0c, y0, yd0, uy0, o_y, o_yd);
     }
 
-    // ---- 80-byte output record: lanes 0..9 store one 8-byte word each
-    {
-        double word = 0.0;
-        const long long packed = (long long)(unsigned)status | ((long long)(unsigned)((itx & 255) | ((ity & 255) << 8) | ((zits & 255) << 16)) << 32);
-        switch (lane) {
-            case 0: word = o_x; break;  case 1: word = o_y; break;  case 2: word = o_z; break;
-            case 3: word = o_xd; break; case 4: word = o_yd; break; case 5: word = o_zd; break;
-            case 6: word = uz0; break;  case 7: word = ux0; break;  case 8: word = uy0; break;
-            case 9: word = __longlong_as_double(packed); break;
-            default: break;
-        }
-        if (out && lane < 10) reinterpret_cast<double*>(out + gi)[lane] = word;
-    }
+    const QOut o = {o_x, o_y, o_z, o_xd, o_yd, o_zd, uz0, ux0, uy0, status, itx, ity};
+    store_record_lanes(out, gi, lane, o, zits);
     if (u_traj) {
         double* dst = u_traj + (size_t)gi * 3 * N;
 #pragma unroll
@@ -561,11 +528,7 @@ __device__ __forceinline__ void tick_affine_body(const DevConst& c, const int gi
             const int n = n0 + r;
             if (n < N) {
                 double vx = 0.0, vy = 0.0;
-                if (stage3) {
-                    const double aa = fabs(a[r]), sa = (a[r] < 0.0) ? -1.0 : 1.0;
-                    vx = fma(sgx * sa, (aa > 0.0) ? fmin(tau0 * aa, hbox) : 0.0, c.midx[idx + n]);
-                    vy = fma(sgy * sa, (aa > 0.0) ? fmin(tau1 * aa, hbox) : 0.0, c.midy[idx + n]);
-                }
+                if (stage3) { vx = box_move(sgx, a[r], tau0, hbox, c.midx[idx + n]); vy = box_move(sgy, a[r], tau1, hbox, c.midy[idx + n]); }
                 dst[n] = u[r]; dst[N + n] = vx; dst[2 * N + n] = vy;
             }
         }
@@ -577,16 +540,7 @@ __device__ __forceinline__ void tick_affine_body(const DevConst& c, const int gi
             if (slot < zbatch) zlist[slot] = gi;            // (an instance appends once per step and the count starts at 0: always true)
         }
     }
-    if (rollout_frame >= 0 && lane == 0 && !deferred && !(status & ISMPC_ST_Z_FAILED)) {   // a failed vertical solve is flagged, never fed back
-        ismpc_tick_in* st = state_rw + gi;
-        st->com_pos[0] = o_x; st->com_pos[1] = o_y; st->com_pos[2] = o_z;
-        st->com_vel[0] = o_xd; st->com_vel[1] = o_yd; st->com_vel[2] = o_zd;
-        st->simulation_time = w.sim;
-        const int ctl = w.ctl + 1;
-        st->control_iter = ctl;
-        st->mpc_iter = (int)floor(ctl * c.cdt / c.dt);     // as written at Controller.cpp:504: 29*0.01/0.01 floors to 28, and parity keeps that
-        st->footstep_counter = w.fc;
-    }
+    if (rollout_frame >= 0 && lane == 0 && !deferred && !(status & ISMPC_ST_Z_FAILED)) store_feedback(c, state_rw + gi, o, w);   // a failed vertical solve is flagged, never fed back
 }
 
 

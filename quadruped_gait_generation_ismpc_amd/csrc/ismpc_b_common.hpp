@@ -65,32 +65,44 @@ __device__ __forceinline__ M2 readlane_m2(const M2& y)
     return (M2){readlane64<LANE>(y.a), readlane64<LANE>(y.b), readlane64<LANE>(y.c), readlane64<LANE>(y.d)};
 }
 
-// sinh(x)/x and (cosh(x)-1)/x^2 as functions of w = x^2.  Taylor to w^7 is exact to < 1 ulp for
-// w <= 0.25 (next term 4e-20); beyond that (lambda dt^2 > 0.25: never on a physical gait) libm.
+// P = sinh(x)/x and Q = (cosh(x)-1)/x^2 as Taylor series in w = x^2, in two Horner halves.  Degree 7 (taylor_high, then taylor_low) is
+// exact to < 1 ulp for w <= 0.25 (next term 4e-20); degree 3 (taylor_low from TAYLOR_P3, TAYLOR_Q3) for w <= 0.004 (next term w^4/9! <=
+// 7e-16 relative to 1) -- and w = lambda dt^2 is <= 0.0025 on a physical gait (lambda <= 25 at dt = 0.01).
+constexpr double TAYLOR_P3 = 1.0 / 5040.0, TAYLOR_Q3 = 1.0 / 40320.0;     // 1/7!, 1/8!: where degree 3 starts
+__device__ __forceinline__ void taylor_high(double w, double& P, double& Q)
+{
+    P = 1.0 / 1307674368000.0;                  Q = 1.0 / 20922789888000.0;             // 1/15!, 1/16!
+    P = fma(P, w, 1.0 / 6227020800.0);          Q = fma(Q, w, 1.0 / 87178291200.0);     // 1/13!, 1/14!
+    P = fma(P, w, 1.0 / 39916800.0);            Q = fma(Q, w, 1.0 / 479001600.0);       // 1/11!, 1/12!
+    P = fma(P, w, 1.0 / 362880.0);              Q = fma(Q, w, 1.0 / 3628800.0);         // 1/9!, 1/10!
+    P = fma(P, w, TAYLOR_P3);                   Q = fma(Q, w, TAYLOR_Q3);
+}
+__device__ __forceinline__ void taylor_low(double w, double& P, double& Q)
+{
+    P = fma(P, w, 1.0 / 120.0);                 Q = fma(Q, w, 1.0 / 720.0);             // 1/5!, 1/6!
+    P = fma(P, w, 1.0 / 6.0);                   Q = fma(Q, w, 1.0 / 24.0);              // 1/3!, 1/4!
+    P = fma(P, w, 1.0);                         Q = fma(Q, w, 0.5);
+}
+// ... beyond w = 0.25 (lambda dt^2 > 1/4: never on a physical gait) libm
 __device__ __forceinline__ void sinhc_coshc(double w, double& P, double& Q)
 {
-    if (__builtin_expect(w <= 0.25, 1)) {
-        P = 1.0 / 1307674368000.0;                 // 1/15!
-        P = fma(P, w, 1.0 / 6227020800.0);            // 1/13!
-        P = fma(P, w, 1.0 / 39916800.0);              // 1/11!
-        P = fma(P, w, 1.0 / 362880.0);                // 1/9!
-        P = fma(P, w, 1.0 / 5040.0);                  // 1/7!
-        P = fma(P, w, 1.0 / 120.0);                   // 1/5!
-        P = fma(P, w, 1.0 / 6.0);                     // 1/3!
-        P = fma(P, w, 1.0);
-        Q = 1.0 / 20922789888000.0;                // 1/16!
-        Q = fma(Q, w, 1.0 / 87178291200.0);           // 1/14!
-        Q = fma(Q, w, 1.0 / 479001600.0);             // 1/12!
-        Q = fma(Q, w, 1.0 / 3628800.0);               // 1/10!
-        Q = fma(Q, w, 1.0 / 40320.0);                 // 1/8!
-        Q = fma(Q, w, 1.0 / 720.0);                   // 1/6!
-        Q = fma(Q, w, 1.0 / 24.0);                    // 1/4!
-        Q = fma(Q, w, 0.5);
-    } else {
+    if (__builtin_expect(w <= 0.25, 1)) { taylor_high(w, P, Q); taylor_low(w, P, Q); }
+    else {
         const double x = sqrt(w);
         P = sinh(x) / x;
         Q = (cosh(x) - 1.0) / w;
     }
+}
+// The entries of A_j, B_j (MPCSolver.cpp:353-361) that differ from 0 / 1: ch1 = cosh(x) - 1 = w Q, s1 = sinh(x) / sqrt(lambda) = dt P,
+// s2 = sqrt(lambda) sinh(x) = lambda dt P -- from the series, and from libm for w > 0.25
+__device__ __forceinline__ void ab_series(double w, double dtn, double le, double P, double Q, double& ch1, double& s1, double& s2)
+{
+    ch1 = w * Q; s1 = dtn * P; s2 = le * s1;
+}
+__device__ __forceinline__ void ab_libm(double w, double dtn, double le, double& ch1, double& s1, double& s2)
+{
+    const double x = sqrt(w);
+    ch1 = cosh(x) - 1.0; s1 = dtn * (sinh(x) / x); s2 = le * s1;
 }
 
 // Per-launch scratch of the inequality fallback of the two-launch form: the LIST of deferred instances (batch ints).  The per-tick
@@ -100,10 +112,19 @@ __host__ __device__ inline size_t zscratch_bytes(int batch) { return 4 * (size_t
 __device__ __forceinline__ int* zlist_of(unsigned char* zmark, int) { return reinterpret_cast<int*>(zmark); }
 // Caller bookkeeping in front of solve(): Controller.cpp:297-304 (enabled) and :310.
 struct Walk { double sim; int mpc, ctl, fc; };
-// (ftsp_t: the step timings of the instance's plan -- c.ftsp_t unless the lanes of a wavefront walk different plans)
+// ... as the in-kernel closed loop applies it before tick `frame` (ftsp_t: the step timings of the instance's plan -- c.ftsp_t unless
+// the lanes of a wavefront walk different plans).  load_walk below states the same rule itself: calling this from it costs
+// ismpc_tick_dense<2, 16> a VGPR.
+__device__ __forceinline__ void advance_walk(const DevConst& c, const double* ftsp_t, Walk& w, int frame)
+{
+    if (w.fc >= 0 && w.fc < c.rows && w.sim >= ftsp_t[w.fc] - 1) { w.ctl = 0; w.mpc = 0; w.fc = w.fc + 1; }
+    w.sim = (double)frame;
+}
+template <class Rec> __device__ __forceinline__ Walk read_walk(Rec* rec) { return (Walk){rec->simulation_time, rec->mpc_iter, rec->control_iter, rec->footstep_counter}; }
+// the bookkeeping a tick runs with: the record's, advanced when the tick is one of a host-driven closed loop (rollout_frame >= 0)
 __device__ __forceinline__ Walk load_walk(const DevConst& c, const double* ftsp_t, const ismpc_tick_in* rec, int rollout_frame)
 {
-    Walk w; w.sim = rec->simulation_time; w.mpc = rec->mpc_iter; w.ctl = rec->control_iter; w.fc = rec->footstep_counter;
+    Walk w = read_walk(rec);
     if (rollout_frame >= 0) {
         if (w.fc >= 0 && w.fc < c.rows && w.sim >= ftsp_t[w.fc] - 1) { w.ctl = 0; w.mpc = 0; w.fc = w.fc + 1; }
         w.sim = (double)rollout_frame;
@@ -141,6 +162,29 @@ __device__ __forceinline__ double frcp(double x)
     return r;
 }
 
+// Slack of the bounds on S u, beyond rounding (MPCSolver.cpp:158-160)
+__device__ __forceinline__ double z_tol(double bound) { return 1e-11 * fmax(1.0, fabs(bound)); }
+// the decision variable of a sample: mid + sg sign(a) min(tau |a|, h)
+__device__ __forceinline__ double box_move(double sg, double a, double tau, double h, double mid)
+{
+    const double sa = (a < 0.0) ? -1.0 : 1.0;
+    return fma(sg * sa, (fabs(a) > 0.0) ? fmin(tau * fabs(a), h) : 0.0, mid);
+}
+// Integration of the vertical axis (MPCSolver.cpp:274-278) ...
+__device__ __forceinline__ void integrate_z(const DevConst& c, double dt_over_mass, double h_des, double z0, double zd0, double uz0, double& z, double& zd, int& status)
+{
+    z = fma(c.dt, zd0, z0);
+    zd = fma(dt_over_mass, uz0, zd0) - c.dt * c.g;
+    if (isnan(z)) { z = h_des; status |= ISMPC_ST_Z_NAN; }
+    if (isnan(zd)) { zd = 0.0; status |= ISMPC_ST_Z_NAN; }
+}
+// ... and of a horizontal one with A(lambda_0) = [A0a, A0b; A0c, A0a], B(lambda_0) = [1 - A0a, -A0c] (MPCSolver.cpp:406-422)
+__device__ __forceinline__ void integrate_xy(double A0a, double A0b, double A0c, double x0, double xd0, double u0, double& x, double& xd)
+{
+    x  = fma(1.0 - A0a, u0, fma(A0a, x0, A0b * xd0));
+    xd = fma(-A0c, u0, fma(A0c, x0, A0a * xd0));
+}
+
 // -DISMPC_STAMPS (diagnostic build, scripts/stamps_b.py): wall-clock stamps (s_memrealtime, 100 MHz) of every wavefront of the
 // per-tick lane-group kernels at a few points of the tick; written to a buffer nothing else reads.
 #ifdef ISMPC_STAMPS
@@ -163,12 +207,44 @@ __device__ __forceinline__ unsigned long long stamp_now()
 struct QState { double x, y, z, xd, yd, zd; Walk w; int ps; };     // ps: the instance's record in c.sets (sweep handles: its parameter set; multi-plan handles: its (set, plan) pair; -1 = invalid)
 struct QOut { double x, y, z, xd, yd, zd, uz0, ux0, uy0; int status, itx, ity; };
 
+// (Rec: const ismpc_tick_in, or a volatile one where another wavefront's code wrote it; ps is the caller's)
+template <class Rec> __device__ __forceinline__ void load_com(Rec* rec, QState& s)
+{
+    s.x = rec->com_pos[0]; s.y = rec->com_pos[1]; s.z = rec->com_pos[2];
+    s.xd = rec->com_vel[0]; s.yd = rec->com_vel[1]; s.zd = rec->com_vel[2];
+}
+template <class Rec> __device__ __forceinline__ void load_state(Rec* rec, QState& s)
+{
+    s.w = read_walk(rec);
+    load_com(rec, s);
+}
+__device__ __forceinline__ void store_state(ismpc_tick_in* rec, const QState& s, const Walk& w)
+{
+    rec->com_pos[0] = s.x; rec->com_pos[1] = s.y; rec->com_pos[2] = s.z;
+    rec->com_vel[0] = s.xd; rec->com_vel[1] = s.yd; rec->com_vel[2] = s.zd;
+    rec->simulation_time = w.sim; rec->mpc_iter = w.mpc; rec->control_iter = w.ctl; rec->footstep_counter = w.fc;
+}
 __device__ __forceinline__ void store_record(ismpc_tick_out* __restrict__ rec, const QOut& o)
 {
     double2* o2 = reinterpret_cast<double2*>(rec);
     const long long packed = (long long)(unsigned)o.status | ((long long)(unsigned)((o.itx & 255) | ((o.ity & 255) << 8)) << 32);
     o2[0] = make_double2(o.x, o.y); o2[1] = make_double2(o.z, o.xd); o2[2] = make_double2(o.yd, o.zd);
     o2[3] = make_double2(o.uz0, o.ux0); o2[4] = make_double2(o.uy0, __longlong_as_double(packed));
+}
+// The same 80-byte record from a wavefront that holds the result in every lane: lanes 0..9 store one 8-byte word each (zits: iterations
+// of the inequality fallback)
+__device__ __forceinline__ void store_record_lanes(ismpc_tick_out* __restrict__ out, int gi, int lane, const QOut& o, int zits)
+{
+    double word = 0.0;
+    const long long packed = (long long)(unsigned)o.status | ((long long)(unsigned)((o.itx & 255) | ((o.ity & 255) << 8) | ((zits & 255) << 16)) << 32);
+    switch (lane) {
+        case 0: word = o.x; break;   case 1: word = o.y; break;   case 2: word = o.z; break;
+        case 3: word = o.xd; break;  case 4: word = o.yd; break;  case 5: word = o.zd; break;
+        case 6: word = o.uz0; break; case 7: word = o.ux0; break; case 8: word = o.uy0; break;
+        case 9: word = __longlong_as_double(packed); break;
+        default: break;
+    }
+    if (out && lane < 10) reinterpret_cast<double*>(out + gi)[lane] = word;
 }
 // Controller.cpp:346-348 (feed the output back), :503-504 (advance the counters)
 __device__ __forceinline__ void store_feedback(const DevConst& c, ismpc_tick_in* __restrict__ st, const QOut& o, const Walk& w)
@@ -178,7 +254,7 @@ __device__ __forceinline__ void store_feedback(const DevConst& c, ismpc_tick_in*
     st->simulation_time = w.sim;
     const int ctl = w.ctl + 1;
     st->control_iter = ctl;
-    st->mpc_iter = (int)floor(ctl * c.cdt / c.dt);     // as written at Controller.cpp:504 (see tick_affine_body)
+    st->mpc_iter = (int)floor(ctl * c.cdt / c.dt);     // as written at Controller.cpp:504: 29*0.01/0.01 floors to 28, and parity keeps that
     st->footstep_counter = w.fc;
 }
 

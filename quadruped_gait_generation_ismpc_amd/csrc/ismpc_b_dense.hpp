@@ -333,19 +333,8 @@ void ismpc_tick_dense(const DevConst c, const ismpc_tick_in* __restrict__ in_ro,
             o_yd = (A0.c * y0 + A0.d * yd0) + B10 * uy0;
         }
 
-        // ---- 80-byte output record: lanes 0..9 store one 8-byte word each
-        {
-            double word = 0.0;
-            const long long packed = (long long)(unsigned)status | ((long long)(unsigned)((itx & 255) | ((ity & 255) << 8)) << 32);
-            switch (lane) {
-                case 0: word = o_x; break;  case 1: word = o_y; break;  case 2: word = o_z; break;
-                case 3: word = o_xd; break; case 4: word = o_yd; break; case 5: word = o_zd; break;
-                case 6: word = uz0; break;  case 7: word = ux0; break;  case 8: word = uy0; break;
-                case 9: word = __longlong_as_double(packed); break;
-                default: break;
-            }
-            if (out && lane < 10) reinterpret_cast<double*>(out + gi)[lane] = word;
-        }
+        const QOut o = {o_x, o_y, o_z, o_xd, o_yd, o_zd, uz0, ux0, uy0, status, itx, ity};
+        store_record_lanes(out, gi, lane, o, 0);
         if (u_traj) {
             double* dst = u_traj + (size_t)gi * 3 * N;
 #pragma unroll
@@ -363,16 +352,7 @@ void ismpc_tick_dense(const DevConst c, const ismpc_tick_in* __restrict__ in_ro,
             }
         }
         // ---- closed loop: feed back (Controller.cpp:346-348) and advance counters (:503-504)
-        if (rollout_frame >= 0 && lane == 0) {
-            ismpc_tick_in* st = state_rw + gi;
-            st->com_pos[0] = o_x; st->com_pos[1] = o_y; st->com_pos[2] = o_z;
-            st->com_vel[0] = o_xd; st->com_vel[1] = o_yd; st->com_vel[2] = o_zd;
-            st->simulation_time = w.sim;
-            const int ctl = w.ctl + 1;
-            st->control_iter = ctl;
-            st->mpc_iter = (int)floor(ctl * c.cdt / c.dt);
-            st->footstep_counter = w.fc;
-        }
+        if (rollout_frame >= 0 && lane == 0) store_feedback(c, state_rw + gi, o, w);
     }
 }
 

@@ -1,7 +1,7 @@
 // Formulation B, part 4 of 4 of the translation unit ismpc_hip.hip: the lane-group family, the default for horizons N <= 128.
 // Per-tick kernels ismpc_tick_quad (two-launch form, with ismpc_tick_affine_fallback behind it), ismpc_tick_quad_inline and
 // ismpc_tick_quad_one (one launch per step), the closed loop inside one launch (ismpc_rollout_quad), and the counting sort of
-// ismpc_sweep_bind (sweep_sort_*, plans_sort_*).
+// ismpc_sweep_bind (sweep_sort_*).
 #pragma once
 #include "ismpc_b_affine.hpp"
 
@@ -157,21 +157,8 @@ template <int R, int LPI> constexpr int wave_lds_double2() { return (64 / LPI) *
 // ... and, in the kernels that run the inequality fallback themselves, at least the fallback's working window (z_active_set)
 template <int R, int LPI> constexpr int wave_lds_double2_fb() { return wave_lds_double2<R, LPI>() > (Z_LDS_DOUBLES + 1) / 2 ? wave_lds_double2<R, LPI>() : (Z_LDS_DOUBLES + 1) / 2; }
 
-// KF: how the knapsack Newton loop is scheduled, not what it computes (the iterates are bit-identical): 0 = count the saturated
-// samples first and form the two sums only for axes that still move (fewest instructions: batches that fill the chip are
-// VALU-issue bound); 1 = count and sums of both axes in one pass, six interleaved group reductions instead of up to three
-// dependent ones per axis.  Measured (scripts/kf_sweep.sh, MI355X): 1 is slower at every batch size -- 10.2 vs 9.7 us at 1 024
-// instances, 14.0 vs 12.8 at 8 192, 51.8 vs 46.7 at 65 536, 5.9 vs 5.4 us per tick in the rollout kernel -- even one wavefront
-// alone on its SIMD is bound by the number of instructions it issues, not by the reduction chains.  Kept as a build-time knob.
-#ifndef ISMPC_KF_INLINE
-#define ISMPC_KF_INLINE 0
-#endif
-#ifndef ISMPC_KF_MAIN
-#define ISMPC_KF_MAIN 0
-#endif
-#ifndef ISMPC_KF_ROLLOUT
-#define ISMPC_KF_ROLLOUT 0
-#endif
+// Tried and dropped for the knapsack loop: count and sums of both axes in one pass (six interleaved reductions) -- slower on MI355X
+// at every size: 10.2 vs 9.7 us at 1 024 instances, 14.0 vs 12.8 at 8 192, 51.8 vs 46.7 at 65 536, 5.9 vs 5.4 per rollout tick.
 // SW: parameter sweep -- the groups of a wavefront may belong to different parameter sets: what depends on the set (tables
 // of the vertical stage, tails, mass, eta, box widths, bounds on S u) is read through the instance's own record c.sets[s.ps]
 // (per-lane loads); horizon, plan, dt, g and the gate are the handle's.  SW = 0 compiles to exactly the plain kernel.
@@ -182,7 +169,7 @@ template <int R, int LPI> constexpr int wave_lds_double2_fb() { return wave_lds_
 // which masks nothing (keep is not read) and compiles to the loop it always had: it sets one simulation time for its whole batch, so its
 // wavefronts hold one gait phase, and both a flight test and a parking mask (valid && alive) measured slower there
 // (scripts/bench_rollout.py, -1 to -3 %).
-template <int R, int LPI, int KF, int SW = 0, bool MF = true>
+template <int R, int LPI, int SW = 0, bool MF = true>
 __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lane, const QState& s, QOut& o, double* __restrict__ u_traj_inst,
                                                 double2* __restrict__ lds_wave, const bool keep)
 {
@@ -258,7 +245,7 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
             if (n < N) { smin = fmin(smin, su[r]); smax = fmax(smax, su[r]); }
         }
     }
-    const double zlo_t = p_z_lo - 1e-11 * fmax(1.0, fabs(p_z_lo)), zhi_t = p_z_hi + 1e-11 * fmax(1.0, fabs(p_z_hi));
+    const double zlo_t = p_z_lo - z_tol(p_z_lo), zhi_t = p_z_hi + z_tol(p_z_hi);
     const bool viol = smin < zlo_t || smax > zhi_t;                                                // MPCSolver.cpp:158-160, beyond rounding
     const unsigned long long vmask = __builtin_amdgcn_ballot_w64(viol);
     const bool deferred = run && (((vmask >> (lane & (64 - LPI))) & ((1ull << LPI) - 1ull)) != 0ull);
@@ -283,15 +270,12 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
             big = big || (wv_[r] > 0.25);
             mid = mid || (wv_[r] > 0.004);
         }
-        if (__builtin_amdgcn_ballot_w64(mid) == 0) {      // degree 3 is exact to < 1 ulp for w <= 0.004 (see tick_affine_body)
+        if (__builtin_amdgcn_ballot_w64(mid) == 0) {      // degree 3 (taylor_low) in every group of the wavefront
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const double wv = wv_[r];
-                double P = 1.0 / 5040.0, Q = 1.0 / 40320.0;
-                P = fma(P, wv, 1.0 / 120.0);         Q = fma(Q, wv, 1.0 / 720.0);
-                P = fma(P, wv, 1.0 / 6.0);           Q = fma(Q, wv, 1.0 / 24.0);
-                P = fma(P, wv, 1.0);                 Q = fma(Q, wv, 0.5);
-                ch1[r] = wv * Q; s1[r] = s1[r] * P; s2[r] = le_[r] * s1[r];
+                double P = TAYLOR_P3, Q = TAYLOR_Q3;
+                taylor_low(wv_[r], P, Q);
+                ab_series(wv_[r], s1[r], le_[r], P, Q, ch1[r], s1[r], s2[r]);
             }
         } else {
             // some group of this wavefront needs the long polynomial.  The choice is made PER GROUP (= per instance): a group whose own
@@ -300,20 +284,13 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
             const bool gmid = ((__builtin_amdgcn_ballot_w64(mid) >> (lane & (64 - LPI))) & ((LPI == 64) ? ~0ull : ((1ull << LPI) - 1ull))) != 0ull;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const double wv = wv_[r], dtn = s1[r];
-                double P = 1.0 / 1307674368000.0, Q = 1.0 / 20922789888000.0;
-                P = fma(P, wv, 1.0 / 6227020800.0);  Q = fma(Q, wv, 1.0 / 87178291200.0);
-                P = fma(P, wv, 1.0 / 39916800.0);    Q = fma(Q, wv, 1.0 / 479001600.0);
-                P = fma(P, wv, 1.0 / 362880.0);      Q = fma(Q, wv, 1.0 / 3628800.0);
-                P = gmid ? fma(P, wv, 1.0 / 5040.0) : 1.0 / 5040.0;   Q = gmid ? fma(Q, wv, 1.0 / 40320.0) : 1.0 / 40320.0;   // (degree 3 starts here)
-                P = fma(P, wv, 1.0 / 120.0);         Q = fma(Q, wv, 1.0 / 720.0);
-                P = fma(P, wv, 1.0 / 6.0);           Q = fma(Q, wv, 1.0 / 24.0);
-                P = fma(P, wv, 1.0);                 Q = fma(Q, wv, 0.5);
-                ch1[r] = wv * Q; s1[r] = dtn * P; s2[r] = le_[r] * s1[r];
-                if (__builtin_amdgcn_ballot_w64(big) != 0 && wv > 0.25) {     // lambda dt^2 > 1/4: off any physical gait; libm
-                    const double x = sqrt(wv);
-                    ch1[r] = cosh(x) - 1.0; s1[r] = dtn * (sinh(x) / x); s2[r] = le_[r] * s1[r];
-                }
+                const double dtn = s1[r];
+                double P, Q;
+                taylor_high(wv_[r], P, Q);
+                P = gmid ? P : TAYLOR_P3;   Q = gmid ? Q : TAYLOR_Q3;   // (degree 3 starts here)
+                taylor_low(wv_[r], P, Q);
+                ab_series(wv_[r], dtn, le_[r], P, Q, ch1[r], s1[r], s2[r]);
+                if (__builtin_amdgcn_ballot_w64(big) != 0 && wv_[r] > 0.25) ab_libm(wv_[r], dtn, le_[r], ch1[r], s1[r], s2[r]);     // lambda dt^2 > 1/4: off any physical gait
             }
         }
     }
@@ -373,76 +350,39 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
             if (Tq[ax] > 1e-300) st3 |= (ax == 0 ? ISMPC_ST_X_INFEASIBLE : ISMPC_ST_Y_INFEASIBLE);
         }
     }
-    if constexpr (KF == 0) {
-        for (int it = 0; it < N + 2; ++it) {
-            if (__builtin_amdgcn_ballot_w64(live[0] || live[1]) == 0ull) break;
+    for (int it = 0; it < N + 2; ++it) {
+        if (__builtin_amdgcn_ballot_w64(live[0] || live[1]) == 0ull) break;
 #pragma unroll
-            for (int ax = 0; ax < 2; ++ax) {
-                if (__builtin_amdgcn_ballot_w64(live[ax]) == 0ull) continue;      // this axis is done in every group of the wavefront (the other one
-                                                                                  // may keep the loop alive: scripts/knapsack_model.py)
-                int cl = 0;
+        for (int ax = 0; ax < 2; ++ax) {
+            if (__builtin_amdgcn_ballot_w64(live[ax]) == 0ull) continue;      // this axis is done in every group of the wavefront (the other one
+                                                                              // may keep the loop alive: scripts/knapsack_model.py)
+            int cl = 0;
 #pragma unroll
-                for (int r = 0; r < R; ++r) cl += (tau[ax] * fabs(a[r]) >= h) ? 1 : 0;
-                const int cnt = Grp<LPI>::sum_i(cl);
-                if (live[ax] && cnt == prev[ax]) live[ax] = false;                // active set unchanged: exact
-                if (__builtin_amdgcn_ballot_w64(live[ax]) == 0ull) continue;
-                double ssat = 0.0, qfree = 0.0;
+            for (int r = 0; r < R; ++r) cl += (tau[ax] * fabs(a[r]) >= h) ? 1 : 0;
+            const int cnt = Grp<LPI>::sum_i(cl);
+            if (live[ax] && cnt == prev[ax]) live[ax] = false;                // active set unchanged: exact
+            if (__builtin_amdgcn_ballot_w64(live[ax]) == 0ull) continue;
+            double ssat = 0.0, qfree = 0.0;
 #pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    // 0 / 1 masks and two fused multiply-adds instead of two 64-bit selects and two adds: the same sums bit for bit
-                    // (fma(1, x, s) = s + x rounded once, fma(0, x, s) = s), a third fewer instructions in the loop the kernel spends most in
-                    const double ab = fabs(a[r]);
-                    const bool sat = tau[ax] * ab >= h;
-                    const double ms = sat ? 1.0 : 0.0, mf = sat ? 0.0 : 1.0;
-                    ssat = fma(ms, ab, ssat); qfree = fma(mf, a[r] * a[r], qfree);
-                }
-                ssat = Grp<LPI>::sum(ssat); qfree = Grp<LPI>::sum(qfree);
-                if (live[ax]) {
-                    ++its[ax];
-                    const double rem = fma(-h, ssat, Tq[ax]);
-                    if (!(qfree > 0.0)) {                                         // everything saturated
-                        if (rem > fma(h * ssat, 1e-12, 1e-300)) st3 |= (ax == 0 ? ISMPC_ST_X_INFEASIBLE : ISMPC_ST_Y_INFEASIBLE);
-                        tau[ax] = INFINITY; live[ax] = false;
-                    } else {
-                        const double tn = rem * frcp(qfree);
-                        if (!(tn > tau[ax])) live[ax] = false;
-                        else { tau[ax] = tn; prev[ax] = cnt; }
-                    }
-                }
+            for (int r = 0; r < R; ++r) {
+                // 0 / 1 masks and two fused multiply-adds instead of two 64-bit selects and two adds: the same sums bit for bit
+                // (fma(1, x, s) = s + x rounded once, fma(0, x, s) = s), a third fewer instructions in the loop the kernel spends most in
+                const double ab = fabs(a[r]);
+                const bool sat = tau[ax] * ab >= h;
+                const double ms = sat ? 1.0 : 0.0, mf = sat ? 0.0 : 1.0;
+                ssat = fma(ms, ab, ssat); qfree = fma(mf, a[r] * a[r], qfree);
             }
-        }
-    } else {
-        for (int it = 0; it < N + 2; ++it) {
-            if (__builtin_amdgcn_ballot_w64(live[0] || live[1]) == 0ull) break;
-            int cl[2] = {0, 0};
-            double ssat[2] = {0.0, 0.0}, qfree[2] = {0.0, 0.0};
-#pragma unroll
-            for (int ax = 0; ax < 2; ++ax) {
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const bool sat = tau[ax] * fabs(a[r]) >= h;
-                    cl[ax] += sat ? 1 : 0; ssat[ax] += sat ? fabs(a[r]) : 0.0;
-                    const double a2 = a[r] * a[r]; qfree[ax] += sat ? 0.0 : a2;
-                }
-            }
-            const int cnt0 = Grp<LPI>::sum_i(cl[0]), cnt1 = Grp<LPI>::sum_i(cl[1]);
-            ssat[0] = Grp<LPI>::sum(ssat[0]); ssat[1] = Grp<LPI>::sum(ssat[1]);
-            qfree[0] = Grp<LPI>::sum(qfree[0]); qfree[1] = Grp<LPI>::sum(qfree[1]);
-#pragma unroll
-            for (int ax = 0; ax < 2; ++ax) {
-                const int cnt = ax == 0 ? cnt0 : cnt1;
-                if (live[ax] && cnt == prev[ax]) live[ax] = false;            // active set unchanged: exact
-                if (live[ax]) {
-                    ++its[ax];
-                    const double rem = fma(-h, ssat[ax], Tq[ax]);
-                    if (!(qfree[ax] > 0.0)) {                                 // everything saturated
-                        if (rem > fma(h * ssat[ax], 1e-12, 1e-300)) st3 |= (ax == 0 ? ISMPC_ST_X_INFEASIBLE : ISMPC_ST_Y_INFEASIBLE);
-                        tau[ax] = INFINITY; live[ax] = false;
-                    } else {
-                        const double tn = rem * frcp(qfree[ax]);
-                        if (!(tn > tau[ax])) live[ax] = false;
-                        else { tau[ax] = tn; prev[ax] = cnt; }
-                    }
+            ssat = Grp<LPI>::sum(ssat); qfree = Grp<LPI>::sum(qfree);
+            if (live[ax]) {
+                ++its[ax];
+                const double rem = fma(-h, ssat, Tq[ax]);
+                if (!(qfree > 0.0)) {                                         // everything saturated
+                    if (rem > fma(h * ssat, 1e-12, 1e-300)) st3 |= (ax == 0 ? ISMPC_ST_X_INFEASIBLE : ISMPC_ST_Y_INFEASIBLE);
+                    tau[ax] = INFINITY; live[ax] = false;
+                } else {
+                    const double tn = rem * frcp(qfree);
+                    if (!(tn > tau[ax])) live[ax] = false;
+                    else { tau[ax] = tn; prev[ax] = cnt; }
                 }
             }
         }
@@ -454,21 +394,15 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
     o.uz0 = 0.0; o.ux0 = 0.0; o.uy0 = 0.0; o.itx = 0; o.ity = 0;
     if (li == 0 && run) {
         o.uz0 = u[0];
-        o.z = fma(dt, zd0, z0);
-        o.zd = fma(p_dt_over_mass, o.uz0, zd0) - dt * c.g;
-        if (isnan(o.z)) { o.z = p_h_des; status |= ISMPC_ST_Z_NAN; }
-        if (isnan(o.zd)) { o.zd = 0.0; status |= ISMPC_ST_Z_NAN; }
+        integrate_z(c, p_dt_over_mass, p_h_des, z0, zd0, o.uz0, o.z, o.zd, status);
         const double A0a = 1.0 + ch1[0], A0b = s1[0], A0c = s2[0];
         if (lam0_l > c.gate) {                                            // MPCSolver.cpp:322
             status |= st3; o.itx = its[0]; o.ity = its[1];
-            const double sa0 = (a[0] < 0.0) ? -1.0 : 1.0;
-            o.ux0 = fma(sgx * sa0, (fabs(a[0]) > 0.0) ? fmin(tau[0] * fabs(a[0]), h) : 0.0, mx0);
-            o.uy0 = fma(sgy * sa0, (fabs(a[0]) > 0.0) ? fmin(tau[1] * fabs(a[0]), h) : 0.0, my0);
+            o.ux0 = box_move(sgx, a[0], tau[0], h, mx0);
+            o.uy0 = box_move(sgy, a[0], tau[1], h, my0);
         } else status |= ISMPC_ST_FLIGHT;
-        o.x  = fma(1.0 - A0a, o.ux0, fma(A0a, x0, A0b * xd0));
-        o.xd = fma(-A0c, o.ux0, fma(A0c, x0, A0a * xd0));
-        o.y  = fma(1.0 - A0a, o.uy0, fma(A0a, y0, A0b * yd0));
-        o.yd = fma(-A0c, o.uy0, fma(A0c, y0, A0a * yd0));
+        integrate_xy(A0a, A0b, A0c, x0, xd0, o.ux0, o.x, o.xd);
+        integrate_xy(A0a, A0b, A0c, y0, yd0, o.uy0, o.y, o.yd);
     }
     o.status = status;
     if (u_traj_inst) {
@@ -478,11 +412,10 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
             if (n < N) {
                 double vx = 0.0, vy = 0.0;
                 if (stage3) {
-                    const double sa = (a[r] < 0.0) ? -1.0 : 1.0;
                     // (SW = 2: the plan's midpoints from the staged window -- the same values, and the pair's record need not stay live)
                     const double2 mq = SW == 2 ? Lm[li * MIDM + r] : make_double2(c.midx[idx + n], c.midy[idx + n]);
-                    vx = fma(sgx * sa, (fabs(a[r]) > 0.0) ? fmin(tau[0] * fabs(a[r]), h) : 0.0, mq.x);
-                    vy = fma(sgy * sa, (fabs(a[r]) > 0.0) ? fmin(tau[1] * fabs(a[r]), h) : 0.0, mq.y);
+                    vx = box_move(sgx, a[r], tau[0], h, mq.x);
+                    vy = box_move(sgy, a[r], tau[1], h, mq.y);
                 }
                 u_traj_inst[n] = run ? u[r] : 0.0; u_traj_inst[N + n] = vx; u_traj_inst[2 * N + n] = vy;
             }
@@ -492,7 +425,7 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
 }
 
 // One launch = one tick: record in, record out (and, in the host-driven closed loop, state fed back in place)
-template <int R, int LPI, int KF, int SW = 0>
+template <int R, int LPI, int SW = 0>
 __device__ __forceinline__ bool tick_group_body(const DevConst& c, const int gi_raw, const int batch, const int lane,
                                                 const ismpc_tick_in* __restrict__ in_ro, ismpc_tick_in* state_rw,
                                                 ismpc_tick_out* __restrict__ out, double* __restrict__ u_traj,
@@ -504,18 +437,15 @@ __device__ __forceinline__ bool tick_group_body(const DevConst& c, const int gi_
     STAMP(0);                                         // first instructions of the wavefront
     const ismpc_tick_in* rec = ((rollout_frame >= 0) ? state_rw : in_ro) + gi;
     QState s;
-    if constexpr (SW == 2) {                          // the instance's pair first: the caller bookkeeping runs on ITS plan's step timings
-        s.ps = record_index<2>(c, rec->reserved);
-        s.w = load_walk(c, c.sets[max(s.ps, 0)].ftsp_t, rec, rollout_frame);
-    } else s.w = load_walk(c, rec, rollout_frame);
-    s.x = rec->com_pos[0]; s.y = rec->com_pos[1]; s.z = rec->com_pos[2];
-    s.xd = rec->com_vel[0]; s.yd = rec->com_vel[1]; s.zd = rec->com_vel[2];
-    if constexpr (SW != 2) {
-        s.ps = 0;
-        if (SW) { const int ps = rec->reserved; s.ps = (ps >= 0 && ps < c.nsets) ? ps : -1; }   // an unknown set: ISMPC_ST_BAD_INDEX, state passed through
-    }
+    // s.ps: the instance's record (-1, an unknown set or pair: ISMPC_ST_BAD_INDEX, state passed through).  A multi-plan
+    // handle needs it first: the caller bookkeeping runs on ITS plan's step timings.  Otherwise it is read last: read
+    // first it costs ismpc_tick_quad_one<13, 8, 2, 1> four spilled VGPRs and 32 bytes of scratch
+    if constexpr (SW == 2) s.ps = record_index<SW>(c, rec->reserved);
+    s.w = load_walk(c, SW == 2 ? c.sets[max(s.ps, 0)].ftsp_t : c.ftsp_t, rec, rollout_frame);
+    load_com(rec, s);
+    if constexpr (SW != 2) s.ps = SW ? record_index<SW>(c, rec->reserved) : 0;
     QOut o;
-    const bool deferred = tick_group_core<R, LPI, KF, SW>(c, lane, s, o, (u_traj && valid) ? u_traj + (size_t)gi * 3 * c.N : nullptr, lds_wave, valid);
+    const bool deferred = tick_group_core<R, LPI, SW>(c, lane, s, o, (u_traj && valid) ? u_traj + (size_t)gi * 3 * c.N : nullptr, lds_wave, valid);
     if ((lane & (LPI - 1)) == 0 && valid) {
         if (out) store_record(out + gi, o);
         if (deferred) {
@@ -544,6 +474,15 @@ template <int SW> __device__ __forceinline__ int slot_instance(const DevConst& c
     if (SW) { if (c.order) return slot < batch ? c.order[slot] : batch; }
     return slot;
 }
+// Front end of the per-tick kernels: where this wavefront stands -- its lane, its index in the workgroup and in the launch (through the
+// virtual block where a sweep is bound).  The wavefront holds the launch slots wave * IPW .. + IPW - 1, lane / LPI picks the group's.
+struct QuadFront { int lane, wv, wave; };
+template <int SW> __device__ __forceinline__ QuadFront quad_front(const DevConst& c)
+{
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int blk = (SW && c.order) ? sweep_vblock(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    return (QuadFront){(int)(threadIdx.x & 63), wv, blk * ISMPC_QUAD_WAVES + wv};
+}
 template <int R, int LPI, int SW = 0>
 __global__ __launch_bounds__(64 * ISMPC_QUAD_WAVES)
 void ismpc_tick_quad(const DevConst c, const ismpc_tick_in* __restrict__ in_ro, ismpc_tick_in* state_rw,
@@ -552,13 +491,10 @@ void ismpc_tick_quad(const DevConst c, const ismpc_tick_in* __restrict__ in_ro, 
 {
     constexpr int IPW = 64 / LPI;                      // instances per wavefront
     __shared__ double2 lds_mid[ISMPC_QUAD_WAVES][wave_lds_double2<R, LPI>()];
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int blk = (SW && c.order) ? sweep_vblock(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-    const int wave = blk * ISMPC_QUAD_WAVES + wv;
-    if (wave * IPW >= batch) return;
-    tick_group_body<R, LPI, ISMPC_KF_MAIN, SW>(c, slot_instance<SW>(c, wave * IPW + lane / LPI, batch), batch, lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id, lds_mid[wv],
-                                               zmark ? zlist_of(zmark, batch) : nullptr);
+    const QuadFront f = quad_front<SW>(c);
+    if (f.wave * IPW >= batch) return;
+    tick_group_body<R, LPI, SW>(c, slot_instance<SW>(c, f.wave * IPW + f.lane / LPI, batch), batch, f.lane, in_ro, state_rw, out, u_traj, rollout_frame,
+                                zmark, launch_id, lds_mid[f.wv], zmark ? zlist_of(zmark, batch) : nullptr);
 }
 
 // Latency variant for small batches (every wavefront resident at once): a wavefront that deferred one of its
@@ -571,17 +507,15 @@ void ismpc_tick_quad_inline(const DevConst c, const ismpc_tick_in* __restrict__ 
 {
     constexpr int IPW = 64 / LPI;
     __shared__ double2 lds_mid[ISMPC_QUAD_WAVES][wave_lds_double2_fb<R, LPI>()];
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wave = blockIdx.x * ISMPC_QUAD_WAVES + wv;
-    if (wave * IPW >= batch) return;
-    const bool def = tick_group_body<R, LPI, ISMPC_KF_INLINE>(c, wave * IPW + lane / LPI, batch, lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id, lds_mid[wv]);
+    const QuadFront f = quad_front<0>(c);
+    if (f.wave * IPW >= batch) return;
+    const bool def = tick_group_body<R, LPI>(c, f.wave * IPW + f.lane / LPI, batch, f.lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id, lds_mid[f.wv]);
     unsigned long long m = __builtin_amdgcn_ballot_w64(def);
     if (m == 0ull) return;
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     for (int q = 0; q < IPW; ++q)
         if ((m >> (LPI * q)) & 1ull)
-            fallback_call<RW>(cdev, wave * IPW + q, lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id, reinterpret_cast<double*>(lds_mid[wv]));   // (the constants in memory:
+            fallback_call<RW>(cdev, f.wave * IPW + q, f.lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id, reinterpret_cast<double*>(lds_mid[f.wv]));   // (the constants in memory:
                                                                                      // taking the address of the by-value argument would move the hot path's copy to the stack)
 }
 
@@ -603,22 +537,19 @@ void ismpc_tick_quad_one(const DevConst c, const ismpc_tick_in* __restrict__ in_
 {
     constexpr int IPW = 64 / LPI;
     __shared__ double2 lds_mid[ISMPC_QUAD_WAVES][wave_lds_double2_fb<R, LPI>()];
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int blk = (SW && c.order) ? sweep_vblock(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-    const int wave = blk * ISMPC_QUAD_WAVES + wv;
-    if (wave * IPW >= batch) return;
-    const bool def = tick_group_body<R, LPI, ISMPC_KF_MAIN, SW>(c, slot_instance<SW>(c, wave * IPW + lane / LPI, batch), batch, lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id, lds_mid[wv]);
+    const QuadFront f = quad_front<SW>(c);
+    if (f.wave * IPW >= batch) return;
+    const bool def = tick_group_body<R, LPI, SW>(c, slot_instance<SW>(c, f.wave * IPW + f.lane / LPI, batch), batch, f.lane, in_ro, state_rw, out, u_traj,
+                                                 rollout_frame, zmark, launch_id, lds_mid[f.wv]);
     unsigned long long m = __builtin_amdgcn_ballot_w64(def);
     if (m == 0ull) return;
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     for (int q = 0; q < IPW; ++q)
         if ((m >> (LPI * q)) & 1ull) {
-            const int gi = __builtin_amdgcn_readfirstlane(slot_instance<SW>(c, wave * IPW + q, batch));
+            const int gi = __builtin_amdgcn_readfirstlane(slot_instance<SW>(c, f.wave * IPW + q, batch));
             const DevConst* cp = cdev;
-            if (SW == 1) cp = c.sets + __builtin_amdgcn_readfirstlane((((rollout_frame >= 0) ? state_rw : in_ro) + gi)->reserved);   // (a deferred instance has a valid set)
-            if (SW == 2) cp = c.sets + __builtin_amdgcn_readfirstlane(record_index<2>(c, (((rollout_frame >= 0) ? state_rw : in_ro) + gi)->reserved));
-            fallback_call_one<RW, one_occ<R, SW>()>(cp, gi, lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id, reinterpret_cast<double*>(lds_mid[wv]));
+            if (SW) cp = c.sets + __builtin_amdgcn_readfirstlane(record_index<SW>(c, (((rollout_frame >= 0) ? state_rw : in_ro) + gi)->reserved));   // (a deferred instance has a valid set / pair)
+            fallback_call_one<RW, one_occ<R, SW>()>(cp, gi, f.lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id, reinterpret_cast<double*>(lds_mid[f.wv]));
         }
 }
 
@@ -651,29 +582,22 @@ void ismpc_rollout_quad(const DevConst c, ismpc_tick_in* state, ismpc_tick_out* 
         if constexpr (FB) { t0 = stop_tick[gi]; if (t0 < 0) continue; }
         ismpc_tick_in* rec = state + gi;
         QState s;
-        s.w.sim = rec->simulation_time; s.w.mpc = rec->mpc_iter; s.w.ctl = rec->control_iter; s.w.fc = rec->footstep_counter;
-        s.x = rec->com_pos[0]; s.y = rec->com_pos[1]; s.z = rec->com_pos[2];
-        s.xd = rec->com_vel[0]; s.yd = rec->com_vel[1]; s.zd = rec->com_vel[2]; s.ps = 0;
-        if (SW) s.ps = record_index<SW>(c, rec->reserved);             // sweep handles: the instance's parameter set; multi-plan handles: its (set, plan) pair
+        load_state(rec, s);
+        s.ps = SW ? record_index<SW>(c, rec->reserved) : 0;            // sweep handles: the instance's parameter set; multi-plan handles: its (set, plan) pair
         const double* ftsp_t = SW == 2 ? c.sets[max(s.ps, 0)].ftsp_t : c.ftsp_t;
         bool alive = true;                                              // FB = false: false once the instance is parked
         int stopped = -1;
         for (int t = t0; t < ticks; ++t) {
             const int frame = first_frame + t;
-            // caller bookkeeping in front of solve(): Controller.cpp:297-304 (enabled) and :310 -- load_walk's rollout branch
+            // caller bookkeeping in front of solve(): Controller.cpp:297-304 (enabled) and :310
             const Walk before = s.w;
-            if (s.w.fc >= 0 && s.w.fc < c.rows && s.w.sim >= ftsp_t[s.w.fc] - 1) { s.w.ctl = 0; s.w.mpc = 0; s.w.fc = s.w.fc + 1; }
-            s.w.sim = (double)frame;
+            advance_walk(c, ftsp_t, s.w, frame);
             QOut o;
-            const bool def = tick_group_core<R, LPI, ISMPC_KF_ROLLOUT, SW, false>(c, lane, s, o, nullptr, lds_mid[wv], true);      // (no mask here: see tick_group_core)
+            const bool def = tick_group_core<R, LPI, SW, false>(c, lane, s, o, nullptr, lds_mid[wv], true);      // (no mask here: see tick_group_core)
             const bool park = def && alive;
             if (li == 0 && valid && alive && !def && traj) store_record(traj + (size_t)t * batch + gi, o);
             // a deferred instance: its pre-tick state goes to memory (FB = false: to stay there; FB = true: for the fallback body)
-            if (park && valid && li == 0) {
-                rec->com_pos[0] = s.x; rec->com_pos[1] = s.y; rec->com_pos[2] = s.z;
-                rec->com_vel[0] = s.xd; rec->com_vel[1] = s.yd; rec->com_vel[2] = s.zd;
-                rec->simulation_time = before.sim; rec->mpc_iter = before.mpc; rec->control_iter = before.ctl; rec->footstep_counter = before.fc;
-            }
+            if (park && valid && li == 0) store_state(rec, s, before);
             if constexpr (!FB) {
                 if (park) { alive = false; stopped = t; }
             }
@@ -689,19 +613,12 @@ void ismpc_rollout_quad(const DevConst c, ismpc_tick_in* state, ismpc_tick_out* 
                     tick_affine_body<RW, true>(SW ? c.sets[__builtin_amdgcn_readfirstlane(max(s.ps, 0))] : c, gi, lane, nullptr, state,
                                                traj ? traj + (size_t)t * batch : nullptr, nullptr, frame, nullptr, 0, nullptr, 0, reinterpret_cast<double*>(lds_mid[wv]));
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-                    const volatile ismpc_tick_in* vr = rec;
-                    s.x = vr->com_pos[0]; s.y = vr->com_pos[1]; s.z = vr->com_pos[2];
-                    s.xd = vr->com_vel[0]; s.yd = vr->com_vel[1]; s.zd = vr->com_vel[2];
-                    s.w.sim = vr->simulation_time; s.w.mpc = vr->mpc_iter; s.w.ctl = vr->control_iter; s.w.fc = vr->footstep_counter;
+                    load_state(static_cast<const volatile ismpc_tick_in*>(rec), s);
                 }
             }
         }
         if (li == 0 && valid) {
-            if (alive) {
-                rec->com_pos[0] = s.x; rec->com_pos[1] = s.y; rec->com_pos[2] = s.z;
-                rec->com_vel[0] = s.xd; rec->com_vel[1] = s.yd; rec->com_vel[2] = s.zd;
-                rec->simulation_time = s.w.sim; rec->mpc_iter = s.w.mpc; rec->control_iter = s.w.ctl; rec->footstep_counter = s.w.fc;
-            }
+            if (alive) store_state(rec, s, s.w);
             if constexpr (!FB) {
                 stop_tick[gi] = stopped;
                 if (stopped >= 0) atomicAdd(c.zflag + 2, 1);
@@ -714,13 +631,20 @@ void ismpc_rollout_quad(const DevConst c, ismpc_tick_in* state, ismpc_tick_out* 
     }
 }
 
-// ---- ismpc_sweep_bind: counting sort of the instances of a batch by parameter set (bucket nsets: records that name no set) ----------
-__global__ __launch_bounds__(256) void sweep_sort_hist(const ismpc_tick_in* __restrict__ in, int batch, int nsets, int* __restrict__ counts)
+// ---- ismpc_sweep_bind: counting sort of the instances of a batch by the record they name -- their parameter set (SW = 1) or, for a multi-plan
+// handle (SW = 2), their (set, plan) pair, set-major: the lane groups of a wavefront then read one set's tables AND one plan's window.  The
+// last bucket takes the instances that name no record.
+template <int SW> __device__ __forceinline__ int sort_bucket(const DevConst& c, int reserved)
+{
+    const int k = record_index<SW>(c, reserved);
+    return k >= 0 ? k : c.nsets * (SW == 2 ? c.nplans : 1);
+}
+template <int SW>
+__global__ __launch_bounds__(256) void sweep_sort_hist(const DevConst c, const ismpc_tick_in* __restrict__ in, int batch, int* __restrict__ counts)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= batch) return;
-    const int ps = in[i].reserved;
-    atomicAdd(counts + ((ps >= 0 && ps < nsets) ? ps : nsets), 1);
+    atomicAdd(counts + sort_bucket<SW>(c, in[i].reserved), 1);
 }
 // exclusive scan of counts[0 .. n) in place (one workgroup; n <= 65 536 + 1 sets, or 2^24 + 1 (set, plan) pairs of a multi-plan handle): counts[k] becomes the first slot of bucket k
 __global__ __launch_bounds__(256) void sweep_sort_scan(int* __restrict__ counts, int n)
@@ -736,28 +660,12 @@ __global__ __launch_bounds__(256) void sweep_sort_scan(int* __restrict__ counts,
     int run = part[tid];
     for (int k = lo; k < hi; ++k) { const int v = counts[k]; counts[k] = run; run += v; }
 }
-__global__ __launch_bounds__(256) void sweep_sort_scatter(const ismpc_tick_in* __restrict__ in, int batch, int nsets, int* __restrict__ cursor, int* __restrict__ order)
+template <int SW>
+__global__ __launch_bounds__(256) void sweep_sort_scatter(const DevConst c, const ismpc_tick_in* __restrict__ in, int batch, int* __restrict__ cursor, int* __restrict__ order)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= batch) return;
-    const int ps = in[i].reserved;
-    order[atomicAdd(cursor + ((ps >= 0 && ps < nsets) ? ps : nsets), 1)] = i;      // (the order INSIDE a bucket is whatever the atomics give: no result depends on it)
-}
-// ... and of a multi-plan handle by (set, plan) pair, set-major (bucket nsets x nplans: records that name no pair): the lane groups of a
-// wavefront then read one set's tables AND one plan's window
-__global__ __launch_bounds__(256) void plans_sort_hist(const DevConst c, const ismpc_tick_in* __restrict__ in, int batch, int* __restrict__ counts)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= batch) return;
-    const int pr = record_index<2>(c, in[i].reserved);
-    atomicAdd(counts + (pr >= 0 ? pr : c.nsets * c.nplans), 1);
-}
-__global__ __launch_bounds__(256) void plans_sort_scatter(const DevConst c, const ismpc_tick_in* __restrict__ in, int batch, int* __restrict__ cursor, int* __restrict__ order)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= batch) return;
-    const int pr = record_index<2>(c, in[i].reserved);
-    order[atomicAdd(cursor + (pr >= 0 ? pr : c.nsets * c.nplans), 1)] = i;
+    order[atomicAdd(cursor + sort_bucket<SW>(c, in[i].reserved), 1)] = i;      // (the order INSIDE a bucket is whatever the atomics give: no result depends on it)
 }
 
 }  // namespace

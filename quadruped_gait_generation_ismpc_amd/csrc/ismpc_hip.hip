@@ -655,11 +655,13 @@ int ismpc_sweep_bind(ismpc_handle* h, int batch, const ismpc_tick_in* in_dev, vo
     int* cursor = h->order + batch;
     HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(int) * (size_t)nb, s));
     const dim3 grid((batch + 255) / 256), block(256);
-    if (h->nplans) hipLaunchKernelGGL(plans_sort_hist, grid, block, 0, s, h->c, in_dev, batch, cursor);
-    else           hipLaunchKernelGGL(sweep_sort_hist, grid, block, 0, s, in_dev, batch, h->c.nsets, cursor);
-    hipLaunchKernelGGL(sweep_sort_scan, dim3(1), block, 0, s, cursor, nb);
-    if (h->nplans) hipLaunchKernelGGL(plans_sort_scatter, grid, block, 0, s, h->c, in_dev, batch, cursor, h->order);
-    else           hipLaunchKernelGGL(sweep_sort_scatter, grid, block, 0, s, in_dev, batch, h->c.nsets, cursor, h->order);
+    with_sw(h, [&](auto SW) {
+        if constexpr (SW != 0) {                     // (neither a sweep nor a multi-plan handle: refused above)
+            hipLaunchKernelGGL(sweep_sort_hist<SW>, grid, block, 0, s, h->c, in_dev, batch, cursor);
+            hipLaunchKernelGGL(sweep_sort_scan, dim3(1), block, 0, s, cursor, nb);
+            hipLaunchKernelGGL(sweep_sort_scatter<SW>, grid, block, 0, s, h->c, in_dev, batch, cursor, h->order);
+        }
+    });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     h->order_batch = batch;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""CPU model of the knapsack Newton loop of the lane-group tick core (csrc/ismpc_b_group.hpp, KF = 0 schedule): how many count and sum
+"""CPU model of the knapsack Newton loop of the lane-group tick core (csrc/ismpc_b_group.hpp): how many count and sum
 passes a wavefront runs per axis when its groups iterate in lockstep, with and without the flight / gate mask on `live`.  No GPU.
 
 The sample is workload.make_batch(100, B).  The oracle's `gi` backend gives the vertical trajectory (want_traj); lambda_j is rebuilt from
