@@ -63,6 +63,8 @@ extern "C" {
 #define ISMPC_ST_Z_NAN         64  /* NaN guard fired (MPCSolver.cpp:277-278)               */
 #define ISMPC_ST_Z_FAILED      128 /* vertical fallback: iteration limit hit or infeasible (the working set may hold
                                       every row of the horizon); never fed back in closed loops */
+/* the bits that say a tick's result is not a solution of the three QPs */
+#define ISMPC_ST_ERROR_MASK (ISMPC_ST_X_INFEASIBLE | ISMPC_ST_Y_INFEASIBLE | ISMPC_ST_BAD_INDEX | ISMPC_ST_Z_FAILED)
 
 /* ---- parameters: parameters.cpp:9-45 and MPCSolver.cpp:253-255 ---------- */
 typedef struct ismpc_params {
@@ -224,6 +226,54 @@ int ismpc_rollout_device(ismpc_handle* h, int batch, ismpc_tick_in* state_dev,
                          int first_frame, int ticks, ismpc_tick_out* traj_dev,
                          void* stream);
 
+/* DISTURBED closed loop with per-instance summaries: ismpc_rollout_device's tick loop (same bookkeeping, same feedback, same
+ * behaviour on error ticks: the loop goes on) with three additions.  Works on every handle ismpc_rollout_device takes (plain, sweep,
+ * multi-plan); runs inside one launch where that one does, and as one launch per tick with two small kernels around it elsewhere
+ * (ISMPC_ROLLOUT=host, N > 128, ISMPC_PATH=dense | wave) -- the same bytes either way.
+ *
+ * PUSHES.  In the reference the state solve() sees comes from the simulator through the Kalman filter and carries whatever pushed
+ * the robot (the impulsive velocity "bang" of quad_walk_no_plots.m:134-144; the push hooks of HRP4WorldNode.cpp:46-71).  Here an
+ * entry adds dv to com_vel of the input state of tick `tick` -- one plain fp64 add per component, applied BEFORE the bookkeeping of
+ * Controller.cpp:297-304,310 (which does not read the velocity, so after it would be the same thing) and before the solve.
+ * pushes_dev holds n_push entries per instance, instance-major (entry j of instance i at [i * n_push + j]), read through a cursor
+ * that starts at entry 0: at tick t the cursor advances over every entry whose tick <= t and applies, in table order, those whose
+ * tick == t.  So a table in ascending order applies every entry; several entries with one tick all apply, one after the other; an
+ * entry behind a larger tick is skipped; a negative tick and a tick >= ticks never apply (INT32_MAX pads unused slots).  Ticks
+ * count from 0 at THIS call, whatever first_frame is.  dv is not validated: it is a state like any other.
+ *
+ * TRAJECTORY.  traj_dev is NULL or (ticks / traj_stride) x batch records; tick t is recorded when (t + 1) % traj_stride == 0, in
+ * row (t + 1) / traj_stride - 1.  traj_stride = 1 is ismpc_rollout_device's layout.
+ *
+ * SUMMARY.  summary_dev is NULL or batch records, one per instance, over the output records of ALL ticks of the call, recorded or
+ * not.  The extrema are taken with fmin / fmax: independent of the order and bit-exact against a host reduction (np.fmin / np.fmax)
+ * of the stride-1 trajectory of the same call.  ticks = 0 gives the empty summary: 0, -1, 0, 0, +inf, -inf, 0, 0.
+ *
+ * With n_push = 0, traj_stride = 1 and summary_dev = NULL the call computes what ismpc_rollout_device computes: trajectory and
+ * final state are byte-identical.  ISMPC_E_INVALID, before the device is touched: null handle, negative batch, ticks or
+ * first_frame, traj_stride < 1, n_push < 0, n_push > 0 with a null table (and, as ismpc_rollout_device, batch > 0 with a null state).
+ * The handle-owned scratch (one record per instance, for ticks that only the summary wants) grows stream-ordered; ismpc_reserve
+ * sizes it beforehand.                                                                                                          */
+typedef struct ismpc_push {          /* 32 bytes */
+    int32_t tick;                    /* tick of THIS call, 0 <= tick < ticks, at which the push applies */
+    int32_t reserved;                /* 0 */
+    double  dv[3];                   /* added to com_vel of the tick's input state, before the solve */
+} ismpc_push;
+
+typedef struct ismpc_rollout_summary {   /* 48 bytes */
+    int32_t status_or;               /* OR of ismpc_tick_out.status over all ticks of the call */
+    int32_t first_error_tick;        /* first tick with status & ISMPC_ST_ERROR_MASK; -1: none */
+    int32_t error_ticks;             /* number of such ticks */
+    int32_t fallback_ticks;          /* ticks with ISMPC_ST_Z_INEQ_ACTIVE */
+    double  com_z_min, com_z_max;    /* over the ticks' output com_pos[2] */
+    double  max_abs_vel[2];          /* max |com_vel[0]|, max |com_vel[1]| over the ticks' outputs */
+} ismpc_rollout_summary;
+
+int ismpc_rollout_mc_device(ismpc_handle* h, int batch, ismpc_tick_in* state_dev, int first_frame, int ticks,
+                            const ismpc_push* pushes_dev, int n_push,      /* batch x n_push, instance-major; NULL with n_push = 0 */
+                            int traj_stride, ismpc_tick_out* traj_dev,     /* NULL, or (ticks / traj_stride) x batch records */
+                            ismpc_rollout_summary* summary_dev,            /* NULL, or batch records */
+                            void* stream);
+
 /* Optional: size the handle's per-launch scratch for batches up to max_batch now (synchronous).  Without it the
  * scratch grows inside the asynchronous entry points with stream-ordered allocations (hipMallocAsync on the caller's
  * stream: no device-wide synchronisation); callers that capture the launches into a hipGraph call this first.  */
@@ -242,10 +292,11 @@ int         ismpc_get_midpoint(const ismpc_handle* h, double* dst, int capacity_
  * deferred list, fallback workgroups done, instances parked by an in-kernel rollout, resume workgroups done.  All four
  * are 0 between calls, whatever was launched before (ticks, rollouts, hipGraph replays of a captured step).          */
 int         ismpc_fallback_counters(ismpc_handle* h, int* out4);
-/* Which kernel the handle's most recent step (ismpc_solve_batch*) or closed loop (ismpc_rollout_device) enqueued, as the host
+/* Which kernel the handle's most recent step (ismpc_solve_batch*) or closed loop (ismpc_rollout_device, ismpc_rollout_mc_device) enqueued, as the host
  * recorded it where it launched (no device work, no synchronisation): out8 = { kernel family (ISMPC_KERNEL_*), lanes per
  * instance, R = horizon samples per lane, RW = samples per lane of the inequality fallback's one-instance-per-wavefront body,
- * bit 0 (1) for the parameter-sweep instantiation and bit 1 (2) for the multi-plan one (3: several sets x several plans), kernels enqueued per step (2 = tick + fallback launch, rollout + resume launch),
+ * bit 0 (1) for the parameter-sweep instantiation, bit 1 (2) for the multi-plan one (3: several sets x several plans) and bit 2 (4) for the
+ * disturbed rollout's (MC = true, ismpc_rollout_mc_device in one launch), kernels enqueued per step (2 = tick + fallback launch, rollout + resume launch),
  * batch, 1 when the ismpc_sweep_bind order placed the instances }.  All zero before the first launch; a closed loop run as
  * one launch per tick (ISMPC_ROLLOUT=host, N > 128) reports its last tick.                                              */
 #define ISMPC_KERNEL_NONE         0

@@ -26,6 +26,11 @@ TICK_IN = np.dtype([("com_pos", "<f8", 3), ("com_vel", "<f8", 3), ("simulation_t
 TICK_OUT = np.dtype([("com_pos", "<f8", 3), ("com_vel", "<f8", 3), ("u0", "<f8", 3),
                      ("status", "<i4"), ("iters", "<i4")], align=False)
 assert TICK_IN.itemsize == 72 and TICK_OUT.itemsize == 80
+# ismpc_push / ismpc_rollout_summary of ismpc_rollout_mc_device
+PUSH = np.dtype([("tick", "<i4"), ("reserved", "<i4"), ("dv", "<f8", 3)], align=False)
+ROLLOUT_SUMMARY = np.dtype([("status_or", "<i4"), ("first_error_tick", "<i4"), ("error_ticks", "<i4"), ("fallback_ticks", "<i4"),
+                            ("com_z_min", "<f8"), ("com_z_max", "<f8"), ("max_abs_vel", "<f8", 2)], align=False)
+assert PUSH.itemsize == 32 and ROLLOUT_SUMMARY.itemsize == 48
 
 # every symbol include/ismpc.h declares
 EXPORTS = ["ismpc_params_default", "ismpc_create", "ismpc_destroy", "ismpc_solve_batch",
@@ -33,7 +38,7 @@ EXPORTS = ["ismpc_params_default", "ismpc_create", "ismpc_destroy", "ismpc_solve
            "ismpc_get_params", "ismpc_midpoint_rows", "ismpc_get_midpoint", "ismpc_set_timing",
            "ismpc_last_kernel_ms", "ismpc_reserve", "ismpc_host_alloc", "ismpc_host_free", "ismpc_host_register",
            "ismpc_host_unregister", "ismpc_create_sweep", "ismpc_sweep_info", "ismpc_sweep_verify_tables", "ismpc_fallback_counters", "ismpc_sweep_bind",
-           "ismpc_last_launch_info", "ismpc_create_plans", "ismpc_plans_info", "ismpc_get_midpoint_plan"]
+           "ismpc_last_launch_info", "ismpc_create_plans", "ismpc_plans_info", "ismpc_get_midpoint_plan", "ismpc_rollout_mc_device"]
 
 _lib = None
 
@@ -66,6 +71,7 @@ def load():
     lib.ismpc_solve_batch.argtypes = [vp, ci, vp, vp]; lib.ismpc_solve_batch.restype = ci
     lib.ismpc_solve_batch_device.argtypes = [vp, ci, vp, vp, vp, vp]; lib.ismpc_solve_batch_device.restype = ci
     lib.ismpc_rollout_device.argtypes = [vp, ci, vp, ci, ci, vp, vp]; lib.ismpc_rollout_device.restype = ci
+    lib.ismpc_rollout_mc_device.argtypes = [vp, ci, vp, ci, ci, vp, ci, ci, vp, vp, vp]; lib.ismpc_rollout_mc_device.restype = ci
     lib.ismpc_abi_version.argtypes = []; lib.ismpc_abi_version.restype = ci
     lib.ismpc_last_error.argtypes = []; lib.ismpc_last_error.restype = C.c_char_p
     lib.ismpc_get_params.argtypes = [vp, C.POINTER(Params)]; lib.ismpc_get_params.restype = ci

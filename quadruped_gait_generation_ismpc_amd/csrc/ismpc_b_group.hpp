@@ -562,16 +562,76 @@ void ismpc_tick_quad_one(const DevConst c, const ismpc_tick_in* __restrict__ in_
 //   FB = true (second launch, exits at once unless the first one parked something): one wavefront per parked instance
 //     resumes it at its tick, running the active-set fallback (all 64 lanes, through memory) at the ticks that need it.
 // Keeping the fallback out of the first kernel keeps its register budget that of the tick itself.
-template <int R, int LPI, int RW, bool FB, int SW = 0>
+//
+// MC = true: the disturbed rollout of ismpc_rollout_mc_device -- per-instance velocity pushes in front of a tick, a trajectory
+// row every `stride` ticks, one ismpc_rollout_summary per instance.  Everything it adds sits under `if constexpr (MC)`; MC = false
+// is the loop above and nothing else.  What lives across tick_group_core (8 lanes, R = 13: 249 VGPRs of 256) stays out of its
+// registers: the push cursor, the tick of the next table entry and the summary accumulators of an instance are one McSlot in an LDS
+// block of their own (never lds_mid, which the core and the fallback use), one slot per lane group of the wavefront.  Every lane of a
+// group reads and rewrites the cursor words with the same values (the state it pushes is group-uniform), lane 0 alone folds the
+// summary: no lane reads what another one wrote.
+//   push: s.xd, s.yd, s.zd += dv, one add per component and entry, in table order, BEFORE the bookkeeping of the tick (which does not
+//     read the velocity) -- so the pre-tick state a deferred instance parks already holds that tick's push;
+//   resume (FB = true): the cursor starts past every entry with tick <= the park tick (they were consumed by the first launch), the
+//     partial summary the first launch left in summary[gi] is reloaded, and the record of a fallback tick -- written by tick_affine_body
+//     through memory -- goes to the handle's scratch record mc.fbrec[gi], whether or not the tick is recorded; from there it is copied
+//     to the row the stride gives it and folded into the summary.
+struct RolloutMc {
+    const ismpc_push* pushes; int n_push;      // batch x n_push, instance-major (NULL with n_push = 0)
+    int stride;                                // tick t goes to row (t + 1) / stride - 1 when (t + 1) % stride == 0
+    ismpc_rollout_summary* summary;            // NULL, or batch records
+    ismpc_tick_out* fbrec;                     // batch scratch records (handle-owned): where the resume launch's fallback ticks leave their record
+};
+struct McSlot { double zmin, zmax, vx, vy; int status_or, first_err, err_ticks, fb_ticks, cursor, next_tick; };      // 56 bytes
+typedef volatile __attribute__((address_space(3))) McSlot LdsSlot;      // ... addressed as LDS (ds_read / ds_write, never a flat access) and volatile: the
+// optimiser would otherwise promote the slot to registers for the length of the tick loop, which is what it exists to avoid.  S below: McSlot or LdsSlot
+template <class S> __device__ __forceinline__ void mc_summary_init(S* a)
+{
+    a->zmin = INFINITY; a->zmax = -INFINITY; a->vx = 0.0; a->vy = 0.0;
+    a->status_or = 0; a->first_err = -1; a->err_ticks = 0; a->fb_ticks = 0;
+}
+template <class S> __device__ __forceinline__ void mc_summary_load(S* a, const ismpc_rollout_summary* s)
+{
+    a->zmin = s->com_z_min; a->zmax = s->com_z_max; a->vx = s->max_abs_vel[0]; a->vy = s->max_abs_vel[1];
+    a->status_or = s->status_or; a->first_err = s->first_error_tick; a->err_ticks = s->error_ticks; a->fb_ticks = s->fallback_ticks;
+}
+template <class S> __device__ __forceinline__ void mc_summary_store(ismpc_rollout_summary* s, const S* a)
+{
+    s->status_or = a->status_or; s->first_error_tick = a->first_err; s->error_ticks = a->err_ticks; s->fallback_ticks = a->fb_ticks;
+    s->com_z_min = a->zmin; s->com_z_max = a->zmax; s->max_abs_vel[0] = a->vx; s->max_abs_vel[1] = a->vy;
+}
+// one tick's record into the summary (fmin / fmax: independent of the order, NaN records leave the extrema alone)
+template <class S> __device__ __forceinline__ void mc_summary_fold(S* a, int status, double z, double xd, double yd, int t)
+{
+    a->status_or |= status;
+    if (status & ISMPC_ST_ERROR_MASK) { if (a->first_err < 0) a->first_err = t; a->err_ticks += 1; }
+    if (status & ISMPC_ST_Z_INEQ_ACTIVE) a->fb_ticks += 1;
+    a->zmin = fmin(a->zmin, z); a->zmax = fmax(a->zmax, z);
+    a->vx = fmax(a->vx, fabs(xd)); a->vy = fmax(a->vy, fabs(yd));
+}
+// the slot of lane group `grp` of wavefront `wv` (MC = false: no LDS, no slot)
+template <bool MC, int IPW> __device__ __forceinline__ LdsSlot* mc_slot_of(int wv, int grp)
+{
+    if constexpr (MC) { __shared__ McSlot mc_lds[ISMPC_QUAD_WAVES * IPW]; return (LdsSlot*)(mc_lds + wv * IPW + grp); }
+    else return nullptr;
+}
+// the first entry at or after `cur` of an instance's table that the cursor rule has not passed once tick `past` is done
+__device__ __forceinline__ int mc_cursor_after(const ismpc_push* pt, int np, int cur, int past)
+{
+    while (cur < np && pt[cur].tick <= past) ++cur;
+    return cur;
+}
+template <int R, int LPI, int RW, bool FB, int SW = 0, bool MC = false>
 __global__ __launch_bounds__(64 * ISMPC_QUAD_WAVES, 2)
 void ismpc_rollout_quad(const DevConst c, ismpc_tick_in* state, ismpc_tick_out* __restrict__ traj, int batch, int first_frame, int ticks,
-                        int* __restrict__ stop_tick, int launch_id)
+                        int* __restrict__ stop_tick, int launch_id, const RolloutMc mc)
 {
     constexpr int IPW = 64 / LPI;
     __shared__ double2 lds_mid[ISMPC_QUAD_WAVES][FB ? wave_lds_double2_fb<R, LPI>() : wave_lds_double2<R, LPI>()];
     const int lane = threadIdx.x & 63, li = lane & (LPI - 1);
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wave = blockIdx.x * ISMPC_QUAD_WAVES + wv;
+    LdsSlot* const slot = mc_slot_of<MC, IPW>(wv, lane / LPI);
     if constexpr (FB) { if (*(volatile int*)(c.zflag + 2) == 0) return; }      // nothing parked (workgroup-uniform: the first launch is done)
     const int nwork = FB ? batch : (batch + IPW - 1) / IPW;          // FB: one instance per wavefront (every group computes it, group 0 stores)
     for (int work = wave; work < nwork; work += FB ? (int)gridDim.x * ISMPC_QUAD_WAVES : nwork) {
@@ -587,14 +647,45 @@ void ismpc_rollout_quad(const DevConst c, ismpc_tick_in* state, ismpc_tick_out* 
         const double* ftsp_t = SW == 2 ? c.sets[max(s.ps, 0)].ftsp_t : c.ftsp_t;
         bool alive = true;                                              // FB = false: false once the instance is parked
         int stopped = -1;
+        int phase = 0, row = 0;                                         // MC: ticks since the last recorded one, next trajectory row (wave-uniform)
+        if constexpr (MC) {
+            // a padding group (FB = false, gi clamped) has no table: it is never pushed and, like everything of it, never stored
+            const int np = (FB || valid) ? mc.n_push : 0;
+            const ismpc_push* pt = mc.pushes + (size_t)gi * mc.n_push;
+            const int cur = FB ? mc_cursor_after(pt, np, 0, t0) : 0;      // (the resume launch: past what the first launch consumed)
+            slot->cursor = cur; slot->next_tick = cur < np ? pt[cur].tick : INT32_MAX;
+            if (FB && mc.summary) mc_summary_load(slot, mc.summary + gi); else mc_summary_init(slot);
+            if constexpr (FB) { const int t0u = __builtin_amdgcn_readfirstlane(t0); phase = t0u % mc.stride; row = t0u / mc.stride; }
+        }
         for (int t = t0; t < ticks; ++t) {
             const int frame = first_frame + t;
+            bool rec_t = true; int trow = t;                            // is this tick recorded, and in which row (MC = false: every tick, row t)
+            if constexpr (MC) {
+                if (slot->next_tick <= t) {                             // the cursor rule of ismpc_rollout_mc_device (include/ismpc.h)
+                    const ismpc_push* pt = mc.pushes + (size_t)gi * mc.n_push;
+                    int cur = slot->cursor, nt;
+                    do {
+                        if (pt[cur].tick == t) { s.xd += pt[cur].dv[0]; s.yd += pt[cur].dv[1]; s.zd += pt[cur].dv[2]; }
+                        ++cur;
+                        nt = cur < mc.n_push ? pt[cur].tick : INT32_MAX;
+                    } while (nt <= t);
+                    slot->cursor = cur; slot->next_tick = nt;
+                }
+                ++phase; rec_t = phase == mc.stride;
+                if (rec_t) { phase = 0; trow = row; ++row; }
+            }
             // caller bookkeeping in front of solve(): Controller.cpp:297-304 (enabled) and :310
             const Walk before = s.w;
             advance_walk(c, ftsp_t, s.w, frame);
             QOut o;
             const bool def = tick_group_core<R, LPI, SW, false>(c, lane, s, o, nullptr, lds_mid[wv], true);      // (no mask here: see tick_group_core)
             const bool park = def && alive;
+            if constexpr (MC) {
+                if (li == 0 && valid && alive && !def) {
+                    if (rec_t && traj) store_record(traj + (size_t)trow * batch + gi, o);
+                    if (mc.summary) mc_summary_fold(slot, o.status, o.z, o.xd, o.yd, t);
+                }
+            } else
             if (li == 0 && valid && alive && !def && traj) store_record(traj + (size_t)t * batch + gi, o);
             // a deferred instance: its pre-tick state goes to memory (FB = false: to stay there; FB = true: for the fallback body)
             if (park && valid && li == 0) store_state(rec, s, before);
@@ -609,16 +700,32 @@ void ismpc_rollout_quad(const DevConst c, ismpc_tick_in* state, ismpc_tick_out* 
             if constexpr (FB) {
                 if (__builtin_amdgcn_ballot_w64(def && valid) != 0ull) {
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                    // the row the fallback body writes its record to (MC: always the scratch record mc.fbrec[gi]; copied and folded below)
+                    ismpc_tick_out* frow = traj ? traj + (size_t)t * batch : nullptr;
+                    if constexpr (MC) frow = mc.fbrec;
+                    // the fallback's working window.  MC: the pointer goes through an empty asm, i.e. the body sees a flat pointer it knows nothing about --
+                    // with a second LDS block in the kernel the ROCm 7.2 gfx950 backend otherwise folds the body's null test of the window into an
+                    // instruction its own verifier rejects (<13, 8, 2, true, 0, true>: "Illegal instruction detected", V_CMP_NE_U32 0, src_shared_base)
+                    double* zwin = reinterpret_cast<double*>(lds_mid[wv]);
+                    if constexpr (MC) asm volatile("" : "+v"(zwin));
                     // (FB: one instance per wavefront, its set is wave-uniform and valid -- an invalid one never defers)
                     tick_affine_body<RW, true>(SW ? c.sets[__builtin_amdgcn_readfirstlane(max(s.ps, 0))] : c, gi, lane, nullptr, state,
-                                               traj ? traj + (size_t)t * batch : nullptr, nullptr, frame, nullptr, 0, nullptr, 0, reinterpret_cast<double*>(lds_mid[wv]));
+                                               frow, nullptr, frame, nullptr, 0, nullptr, 0, zwin);
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
                     load_state(static_cast<const volatile ismpc_tick_in*>(rec), s);
+                    if constexpr (MC) {
+                        // lane k copies the word it wrote itself (store_record_lanes) to the row the stride gives the tick; lane 0 folds the record
+                        const volatile ismpc_tick_out* fr = mc.fbrec + gi;
+                        if (rec_t && traj && lane < 10)
+                            reinterpret_cast<double*>(traj + (size_t)trow * batch + gi)[lane] = reinterpret_cast<const volatile double*>(fr)[lane];
+                        if (mc.summary && li == 0 && valid) mc_summary_fold(slot, fr->status, fr->com_pos[2], fr->com_vel[0], fr->com_vel[1], t);
+                    }
                 }
             }
         }
         if (li == 0 && valid) {
             if (alive) store_state(rec, s, s.w);
+            if constexpr (MC) { if (mc.summary) mc_summary_store(mc.summary + gi, slot); }      // (FB = false, parked: the ticks before the park)
             if constexpr (!FB) {
                 stop_tick[gi] = stopped;
                 if (stopped >= 0) atomicAdd(c.zflag + 2, 1);
@@ -629,6 +736,31 @@ void ismpc_rollout_quad(const DevConst c, ismpc_tick_in* state, ismpc_tick_out* 
         __syncthreads();
         if (threadIdx.x == 0 && atomicAdd(c.zflag + 3, 1) == (int)gridDim.x - 1) { c.zflag[2] = 0; c.zflag[3] = 0; __threadfence(); }
     }
+}
+
+// The same semantics for handles that run their closed loop as one launch per tick (ISMPC_ROLLOUT=host, N > 128, the dense path): two
+// elementwise kernels around the tick's launch, one thread per instance.  ismpc_mc_push applies tick t's entries to the state records --
+// the cursor is rebuilt from the table (where it stands once tick t - 1 is done), so nothing is carried between launches;
+// ismpc_mc_fold folds the tick's records into the summaries (recs == NULL: sets them to the empty summary).
+__global__ __launch_bounds__(256) void ismpc_mc_push(ismpc_tick_in* state, int batch, const ismpc_push* __restrict__ pushes, int n_push, int t)
+{
+    const int gi = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gi >= batch) return;
+    const ismpc_push* pt = pushes + (size_t)gi * n_push;
+    double* v = state[gi].com_vel;
+    for (int cur = mc_cursor_after(pt, n_push, 0, t - 1); cur < n_push && pt[cur].tick <= t; ++cur)
+        if (pt[cur].tick == t) { v[0] += pt[cur].dv[0]; v[1] += pt[cur].dv[1]; v[2] += pt[cur].dv[2]; }
+}
+__global__ __launch_bounds__(256) void ismpc_mc_fold(const ismpc_tick_out* __restrict__ recs, int batch, ismpc_rollout_summary* summary, int t)
+{
+    const int gi = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gi >= batch) return;
+    McSlot a;
+    if (recs) {
+        mc_summary_load(&a, summary + gi);
+        mc_summary_fold(&a, recs[gi].status, recs[gi].com_pos[2], recs[gi].com_vel[0], recs[gi].com_vel[1], t);
+    } else mc_summary_init(&a);
+    mc_summary_store(summary + gi, &a);
 }
 
 // ---- ismpc_sweep_bind: counting sort of the instances of a batch by the record they name -- their parameter set (SW = 1) or, for a multi-plan

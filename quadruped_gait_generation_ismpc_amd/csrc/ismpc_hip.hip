@@ -28,7 +28,8 @@
 //                        larger batches: ismpc_tick_quad_one, one launch, unless a recent launch deferred instances -- then
 //                        ismpc_tick_quad + ismpc_tick_affine_fallback; parameter sweeps: the SW = 1 instantiations of the latter two,
 //                        multi-plan handles (ismpc_create_plans): their SW = 2 instantiations
-//   closed loops         ismpc_rollout_quad, the whole loop in one launch (ISMPC_ROLLOUT=host: one launch per tick)
+//   closed loops         ismpc_rollout_quad, the whole loop in one launch (ISMPC_ROLLOUT=host: one launch per tick); its MC = true
+//                        instantiations for ismpc_rollout_mc_device (pushes, trajectory stride, per-instance summaries)
 //
 // There is no CPU fallback in this file: every entry point needs a HIP device.
 #include <hip/hip_runtime.h>
@@ -84,6 +85,7 @@ struct ismpc_handle {
     int force_waves = 0;      // dense path: 4, 8 or 16 wavefronts per workgroup (0 = 16)
     unsigned char* zmark = nullptr; int zmark_cap = 0; int launch_id = 0; bool z_fallback = true;
     int* zstop = nullptr; int zstop_cap = 0;     // in-kernel rollouts: tick at which an instance was handed to the resume launch (-1: never)
+    ismpc_tick_out* mcrec = nullptr; int mcrec_cap = 0;   // ismpc_rollout_mc_device: one scratch record per instance (a tick that only the summary wants)
     bool dense_path = false;  // true: per-tick MFMA solve (ismpc_tick_dense); false: affine tables (ismpc_tick_affine)
     int cus = 0;              // compute units of the device (kernel variant selection); 0: never the one-launch variant
     bool quad_path = true;    // affine tables, several instances per wavefront (ismpc_tick_quad) where it applies; ISMPC_PATH=wave: one per wavefront
@@ -733,6 +735,7 @@ void ismpc_destroy(ismpc_handle* h)
     if (h->zmark) (void)hipFree(h->zmark);
     if (h->order) (void)hipFree(h->order);
     if (h->zstop) (void)hipFree(h->zstop);
+    if (h->mcrec) (void)hipFree(h->mcrec);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -827,14 +830,17 @@ int ismpc_solve_batch(ismpc_handle* h, int batch, const ismpc_tick_in* in_host, 
     return ISMPC_OK;
 }
 
-int ismpc_rollout_device(ismpc_handle* h, int batch, ismpc_tick_in* state_dev, int first_frame, int ticks,
-                         ismpc_tick_out* traj_dev, void* stream)
+// The closed loop of ismpc_rollout_device and of ismpc_rollout_mc_device (mc = true: pushes, trajectory stride, summaries): ONE host launch
+// function for both, in the kernel (ismpc_rollout_quad, MC = mc) where the handle runs its loops there, one launch per tick otherwise.
+static int rollout_impl(ismpc_handle* h, int batch, ismpc_tick_in* state_dev, int first_frame, int ticks, bool mc, const ismpc_push* pushes_dev,
+                        int n_push, int traj_stride, ismpc_tick_out* traj_dev, ismpc_rollout_summary* summary_dev, hipStream_t s)
 {
-    if (!h || batch < 0 || ticks < 0 || first_frame < 0 || (batch > 0 && !state_dev)) return fail(ISMPC_E_INVALID, "bad argument");
     ON_DEVICE(h);
-    hipStream_t s = static_cast<hipStream_t>(stream);
     StreamMark mark_{h, s};
     if (h->timing) HIP_TRY(hipEventRecord(h->ev0, s));
+    // the scratch record per instance: where a tick leaves its record for the summary and the resume launch its fallback ticks
+    if (mc && batch > h->mcrec_cap)              // stream-ordered growth, as zmark (ismpc_reserve sizes it beforehand)
+        ISMPC_GROW_ASYNC(fail, h, h->mcrec, h->mcrec_cap, batch, sizeof(ismpc_tick_out) * (size_t)batch, s);
     if (batch > 0 && ticks > 0 && h->kernel_rollout && !h->dense_path && h->quad_path && h->c.N <= 128 && h->z_fallback) {
         // the whole closed loop in ONE launch: state in registers, one trajectory record per tick (ismpc_rollout_quad)
         const QuadLaunch q = quad_launch(h, batch, false);
@@ -842,30 +848,64 @@ int ismpc_rollout_device(ismpc_handle* h, int batch, ismpc_tick_in* state_dev, i
             ISMPC_GROW_ASYNC(fail, h, h->zstop, h->zstop_cap, batch, sizeof(int) * (size_t)batch, s);
         const int lid = ++h->launch_id;
         const dim3 rgrid(std::min((batch + ISMPC_QUAD_WAVES - 1) / ISMPC_QUAD_WAVES, 64));
-        const int rc = with_sw(h, [&](auto SW) {
-            constexpr int sw = decltype(SW)::value;
-            return quad_shape(h->c.N, q.lpi, [&](auto RR, auto LL, auto RW_) {
-                if constexpr (has_rollout_quad(LL, sw)) {
-                    // the rollout itself, then its resume launch (FB = true)
-                    hipLaunchKernelGGL((ismpc_rollout_quad<RR, LL, RW_, false, sw>), q.grid, q.block, 0, s, q.c, state_dev, traj_dev, batch, first_frame, ticks, h->zstop, lid);
-                    hipLaunchKernelGGL((ismpc_rollout_quad<RR, LL, RW_, true, sw>), rgrid, q.block, 0, s, q.c, state_dev, traj_dev, batch, first_frame, ticks, h->zstop, lid);
-                    const int v[8] = {ISMPC_KERNEL_ROLLOUT_QUAD, LL, RR, RW_, form_bits(h), 2, batch, 0};      // (ismpc_last_launch_info: the rollout and its resume launch)
-                    std::memcpy(h->last_launch, v, sizeof(v));
-                    return ISMPC_OK;
-                } else      // (a sweep handle rolls out at 16 lanes per instance: the SW = 1 kernels are instantiated for that shape only)
-                    return fail(ISMPC_E_UNSUPPORTED, "parameter sweep: rollouts take 16 lanes per instance");
+        const RolloutMc m{pushes_dev, n_push, traj_stride, summary_dev, h->mcrec};
+        auto both = [&](auto MC_) {
+            constexpr bool MCv = decltype(MC_)::value;
+            return with_sw(h, [&](auto SW) {
+                constexpr int sw = decltype(SW)::value;
+                return quad_shape(h->c.N, q.lpi, [&](auto RR, auto LL, auto RW_) {
+                    if constexpr (has_rollout_quad(LL, sw)) {
+                        // the rollout itself, then its resume launch (FB = true)
+                        hipLaunchKernelGGL((ismpc_rollout_quad<RR, LL, RW_, false, sw, MCv>), q.grid, q.block, 0, s, q.c, state_dev, traj_dev, batch, first_frame, ticks, h->zstop, lid, m);
+                        hipLaunchKernelGGL((ismpc_rollout_quad<RR, LL, RW_, true, sw, MCv>), rgrid, q.block, 0, s, q.c, state_dev, traj_dev, batch, first_frame, ticks, h->zstop, lid, m);
+                        const int v[8] = {ISMPC_KERNEL_ROLLOUT_QUAD, LL, RR, RW_, form_bits(h) | (MCv ? 4 : 0), 2, batch, 0};      // (ismpc_last_launch_info: the rollout and its resume launch)
+                        std::memcpy(h->last_launch, v, sizeof(v));
+                        return ISMPC_OK;
+                    } else      // (a sweep handle rolls out at 16 lanes per instance: the SW = 1 kernels are instantiated for that shape only)
+                        return fail(ISMPC_E_UNSUPPORTED, "parameter sweep: rollouts take 16 lanes per instance");
+                });
             });
-        });
+        };
+        const int rc = mc ? both(std::true_type{}) : both(std::false_type{});
         if (rc != ISMPC_OK) return rc;
         HIP_TRY(hipGetLastError());
     } else {
+        // one launch per tick; the disturbed form puts its two elementwise kernels around it and chooses the trajectory row here
+        const dim3 egrid((batch + 255) / 256), eblock(256);
+        if (summary_dev && batch > 0) hipLaunchKernelGGL(ismpc_mc_fold, egrid, eblock, 0, s, nullptr, batch, summary_dev, 0);      // (the empty summary)
         for (int t = 0; t < ticks; ++t) {
-            int rc = launch(h, batch, nullptr, state_dev, traj_dev ? traj_dev + (size_t)t * batch : nullptr, nullptr, first_frame + t, s);
+            if (n_push > 0 && batch > 0) hipLaunchKernelGGL(ismpc_mc_push, egrid, eblock, 0, s, state_dev, batch, pushes_dev, n_push, t);
+            const bool rec_t = (t + 1) % traj_stride == 0;
+            ismpc_tick_out* out = (rec_t && traj_dev) ? traj_dev + (size_t)((t + 1) / traj_stride - 1) * batch : (summary_dev ? h->mcrec : nullptr);
+            int rc = launch(h, batch, nullptr, state_dev, out, nullptr, first_frame + t, s);
             if (rc != ISMPC_OK) return rc;
+            if (summary_dev && batch > 0) hipLaunchKernelGGL(ismpc_mc_fold, egrid, eblock, 0, s, out, batch, summary_dev, t);
         }
+        if (mc) HIP_TRY(hipGetLastError());
     }
     if (h->timing) { HIP_TRY(hipEventRecord(h->ev1, s)); h->timed_pending = true; }
     return ISMPC_OK;
+}
+
+int ismpc_rollout_device(ismpc_handle* h, int batch, ismpc_tick_in* state_dev, int first_frame, int ticks,
+                         ismpc_tick_out* traj_dev, void* stream)
+{
+    if (!h || batch < 0 || ticks < 0 || first_frame < 0 || (batch > 0 && !state_dev)) return fail(ISMPC_E_INVALID, "bad argument");
+    return rollout_impl(h, batch, state_dev, first_frame, ticks, false, nullptr, 0, 1, traj_dev, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int ismpc_rollout_mc_device(ismpc_handle* h, int batch, ismpc_tick_in* state_dev, int first_frame, int ticks,
+                            const ismpc_push* pushes_dev, int n_push, int traj_stride, ismpc_tick_out* traj_dev,
+                            ismpc_rollout_summary* summary_dev, void* stream)
+{
+    // (what can be said about the numbers is said first: each message is reachable without a handle, i.e. without a device)
+    if (batch < 0 || ticks < 0 || first_frame < 0) return fail(ISMPC_E_INVALID, "ismpc_rollout_mc_device: negative batch, ticks or first_frame");
+    if (traj_stride < 1) return fail(ISMPC_E_INVALID, "ismpc_rollout_mc_device: traj_stride must be at least 1");
+    if (n_push < 0) return fail(ISMPC_E_INVALID, "ismpc_rollout_mc_device: negative n_push");
+    if (n_push > 0 && !pushes_dev) return fail(ISMPC_E_INVALID, "ismpc_rollout_mc_device: n_push > 0 with a null push table");
+    if (!h) return fail(ISMPC_E_INVALID, "ismpc_rollout_mc_device: null handle");
+    if (batch > 0 && !state_dev) return fail(ISMPC_E_INVALID, "ismpc_rollout_mc_device: null state");
+    return rollout_impl(h, batch, state_dev, first_frame, ticks, true, pushes_dev, n_push, traj_stride, traj_dev, summary_dev, static_cast<hipStream_t>(stream));
 }
 
 // Page-locked host memory for callers without HIP headers (the pipelined ismpc_solve_batch needs it on both sides).
@@ -903,6 +943,7 @@ int ismpc_reserve(ismpc_handle* h, int max_batch)
     ON_DEVICE(h);
     if (h->z_fallback && max_batch > h->zmark_cap) ISMPC_GROW_SYNC(fail, h->zmark, h->zmark_cap, max_batch, zscratch_bytes(max_batch));
     if (max_batch > h->zstop_cap) ISMPC_GROW_SYNC(fail, h->zstop, h->zstop_cap, max_batch, sizeof(int) * (size_t)max_batch);
+    if (max_batch > h->mcrec_cap) ISMPC_GROW_SYNC(fail, h->mcrec, h->mcrec_cap, max_batch, sizeof(ismpc_tick_out) * (size_t)max_batch);
     return ISMPC_OK;
 }
 

@@ -13,7 +13,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import Params, TICK_IN, TICK_OUT
+from ._lib import Params, TICK_IN, TICK_OUT, PUSH, ROLLOUT_SUMMARY
 
 ST_X_INFEASIBLE, ST_Y_INFEASIBLE, ST_Z_INEQ_ACTIVE, ST_BAD_INDEX = 1, 2, 4, 8
 ST_FLIGHT, ST_TICK_SKIPPED, ST_Z_NAN, ST_Z_FAILED = 16, 32, 64, 128
@@ -227,6 +227,16 @@ class MPCSolver:
                                                    C.c_void_p(traj_ptr) if traj_ptr else None,
                                                    C.c_void_p(stream) if stream else None))
 
+    def rollout_mc_device(self, batch, state_ptr, first_frame, ticks, pushes_ptr=None, n_push=0, stride=1, traj_ptr=None,
+                          summary_ptr=None, stream=None):
+        """ismpc_rollout_mc_device on raw device pointers: the closed loop with per-instance velocity pushes (batch x n_push
+        ismpc_push entries, instance-major), a trajectory row every `stride` ticks and one ismpc_rollout_summary per instance."""
+        self._check(self._lib.ismpc_rollout_mc_device(self._h, int(batch), C.c_void_p(state_ptr), int(first_frame), int(ticks),
+                                                      C.c_void_p(pushes_ptr) if pushes_ptr else None, int(n_push), int(stride),
+                                                      C.c_void_p(traj_ptr) if traj_ptr else None,
+                                                      C.c_void_p(summary_ptr) if summary_ptr else None,
+                                                      C.c_void_p(stream) if stream else None))
+
     def reserve(self, max_batch):
         """Sizes the handle's per-launch scratch now (ismpc_reserve): callers that capture launches into a hipGraph call this first."""
         self._check(self._lib.ismpc_reserve(self._h, int(max_batch)))
@@ -248,6 +258,8 @@ class MPCSolver:
                 "batch": v[6], "bound_order": bool(v[7])}
         if v[4] & 2:
             info["plans"] = True
+        if v[4] & 4:                                 # the disturbed rollout's instantiation (rollout_mc_*), same rule
+            info["mc"] = True
         return info
 
     def set_timing(self, enabled=True):
@@ -283,6 +295,25 @@ class MPCSolver:
         stream = torch.cuda.current_stream(state_u8.device).cuda_stream
         self.rollout_device(b, state_u8.data_ptr(), first_frame, ticks, traj.data_ptr() if want_traj else None, stream)
         return traj
+
+    def rollout_mc_torch(self, state_u8, first_frame, ticks, pushes=None, stride=1, want_traj=True, want_summary=True):
+        """The disturbed closed loop on torch tensors.  state_u8: CUDA uint8 [batch, 72], updated in place; pushes: None or a CUDA uint8
+        tensor [batch, n_push, 32] of PUSH records (to_device(records).view(batch, n_push, 32)).  Returns (traj, summary): CUDA uint8
+        [ticks // stride, batch, 80] or None, and CUDA uint8 [batch, 48] (ROLLOUT_SUMMARY records) or None."""
+        import torch
+        b = state_u8.shape[0]
+        assert state_u8.is_cuda and state_u8.dtype == torch.uint8 and state_u8.shape[1] == 72 and state_u8.is_contiguous()
+        n_push = 0
+        if pushes is not None:
+            assert pushes.is_cuda and pushes.dtype == torch.uint8 and pushes.dim() == 3 and pushes.shape[0] == b and pushes.shape[2] == 32 and pushes.is_contiguous()
+            assert pushes.device == state_u8.device
+            n_push = int(pushes.shape[1])
+        traj = torch.empty((ticks // stride if stride >= 1 else 0, b, 80), dtype=torch.uint8, device=state_u8.device) if want_traj else None
+        summary = torch.empty((b, 48), dtype=torch.uint8, device=state_u8.device) if want_summary else None
+        stream = torch.cuda.current_stream(state_u8.device).cuda_stream
+        self.rollout_mc_device(b, state_u8.data_ptr(), first_frame, ticks, pushes.data_ptr() if n_push else None, n_push, stride,
+                               traj.data_ptr() if want_traj else None, summary.data_ptr() if want_summary else None, stream)
+        return traj, summary
 
 
 def to_device(records, device="cuda:0"):
