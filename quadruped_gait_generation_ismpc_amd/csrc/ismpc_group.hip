@@ -23,6 +23,7 @@
 
 #include "ismpc_group.h"
 #include "ismpc_host.hpp"
+#include "ismpc_rccl_load.hpp"
 
 namespace {
 
@@ -34,7 +35,7 @@ int gfail(int code, const std::string& msg) { g_gerr = msg; return code; }
 // A process that already maps a copy of RCCL (a torch process maps torch/lib/librccl.so, which has no SONAME) must not get a
 // second one: the copy found in /proc/self/maps is opened by its path; otherwise $ISMPC_RCCL_LIB, then librccl.so.1.
 struct Rccl {
-    void* lib = nullptr; std::string err, path;
+    void* lib = nullptr; std::string err, path; bool test_double = false;
     decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
     decltype(&ncclCommInitRank) CommInitRank = nullptr;
     decltype(&ncclCommInitAll) CommInitAll = nullptr;
@@ -54,14 +55,7 @@ std::string mapped_rccl()
     FILE* f = std::fopen("/proc/self/maps", "r");
     if (!f) return "";
     char line[4096]; std::string found;
-    while (std::fgets(line, sizeof line, f)) {
-        const char* p = std::strstr(line, "librccl.so");
-        if (!p) continue;
-        const char* s = std::strchr(line, '/');
-        if (!s) continue;
-        found.assign(s); while (!found.empty() && (found.back() == '\n' || found.back() == ' ')) found.pop_back();
-        break;
-    }
+    while (found.empty() && std::fgets(line, sizeof line, f)) found = ismpc_rccl::maps_line_path(line);
     std::fclose(f);
     return found;
 }
@@ -74,16 +68,15 @@ void load_rccl()
     if (!m.empty()) tries.push_back(m);
     if (const char* e = std::getenv("ISMPC_RCCL_LIB")) tries.push_back(e);
     tries.push_back("librccl.so.1"); tries.push_back("/opt/rocm/lib/librccl.so.1"); tries.push_back("librccl.so");
-    for (const std::string& t : tries) {
-        r.lib = dlopen(t.c_str(), RTLD_NOW | RTLD_LOCAL);
-        if (r.lib) { r.path = t; break; }
-        r.err += t + ": " + (dlerror() ? dlerror() : "?") + "; ";
-    }
+    const ismpc_rccl::Opened o = ismpc_rccl::open_first(tries);
+    r.lib = o.lib; r.path = o.path; r.err = o.error_text();
     if (!r.lib) return;
 #define BIND(name) r.name = reinterpret_cast<decltype(r.name)>(dlsym(r.lib, "nccl" #name)); if (!r.name) { r.err = "nccl" #name " missing in " + r.path; r.lib = nullptr; return; }
     BIND(GetUniqueId) BIND(CommInitRank) BIND(CommInitAll) BIND(CommDestroy) BIND(CommCount) BIND(AllGather) BIND(Broadcast)
     BIND(GroupStart) BIND(GroupEnd) BIND(GetErrorString) BIND(GetVersion)
 #undef BIND
+    // the in-process test double of tests/helpers/fake_rccl.cpp runs several ranks on ONE device; no RCCL exports this symbol
+    r.test_double = dlsym(r.lib, "ismpc_test_rccl_double") != nullptr;
 }
 Rccl* rccl()
 {
@@ -281,7 +274,8 @@ int check_devices(const int* devices, int n)
     if (hipGetDeviceCount(&have) != hipSuccess || have < 1) { (void)hipGetLastError(); return gfail(ISMPC_E_NO_DEVICE, "no HIP device: the ISMPC hot path has no CPU fallback"); }
     for (int k = 0; k < n; ++k) {
         if (devices[k] < 0 || devices[k] >= have) return gfail(ISMPC_E_INVALID, "device ordinal " + std::to_string(devices[k]) + " outside [0, " + std::to_string(have) + ")");
-        for (int j = 0; j < k; ++j) if (devices[j] == devices[k]) return gfail(ISMPC_E_INVALID, "a device appears twice in the group (RCCL needs one rank per GPU)");
+        for (int j = 0; j < k; ++j) if (devices[j] == devices[k] && !(rccl() && g_rccl.test_double))
+            return gfail(ISMPC_E_INVALID, "a device appears twice in the group (RCCL needs one rank per GPU)");
     }
     return ISMPC_OK;
 }
