@@ -186,7 +186,8 @@ __device__ __forceinline__ void integrate_xy(double A0a, double A0b, double A0c,
 }
 
 // -DISMPC_STAMPS (diagnostic build, scripts/stamps_b.py): wall-clock stamps (s_memrealtime, 100 MHz) of every wavefront of the
-// per-tick lane-group kernels at a few points of the tick; written to a buffer nothing else reads.
+// per-tick lane-group kernels at a few points of the tick (words 0..5 of its eight) and the hardware slot it ran in (word 6); written to a
+// buffer nothing else reads.
 #ifdef ISMPC_STAMPS
 __device__ unsigned long long g_stamps[16384 * 8];
 __device__ __forceinline__ unsigned long long stamp_now()
@@ -195,10 +196,19 @@ __device__ __forceinline__ unsigned long long stamp_now()
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
     return t;
 }
+// where the wavefront ran (scripts/slot_timeline.py): HW_ID (wave slot [3:0], SIMD [5:4], CU [11:8], SH [12], SE [15:13]) in the low word, XCC_ID above it
+__device__ __forceinline__ unsigned long long stamp_where()
+{
+    unsigned hw, xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)\n\ts_getreg_b32 %1, hwreg(HW_REG_XCC_ID)" : "=s"(hw), "=s"(xcc));
+    return (unsigned long long)hw | ((unsigned long long)xcc << 32);
+}
+#define STAMP_WHERE do { if (g_stamp_wave >= 0 && g_stamp_wave < 16384) { const unsigned long long w_ = stamp_where(); if ((threadIdx.x & 63) == 0) g_stamps[g_stamp_wave * 8 + 6] = w_; } } while (0)
 #define STAMP(k_) do { if (g_stamp_wave >= 0 && g_stamp_wave < 16384) { const unsigned long long t_ = stamp_now(); if ((threadIdx.x & 63) == 0) g_stamps[g_stamp_wave * 8 + (k_)] = t_; } } while (0)
 #define STAMP_DECL const int g_stamp_wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)
 #else
 #define STAMP(k_) do {} while (0)
+#define STAMP_WHERE do {} while (0)
 #define STAMP_DECL do {} while (0)
 #endif
 

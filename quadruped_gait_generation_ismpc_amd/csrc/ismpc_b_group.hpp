@@ -455,6 +455,7 @@ __device__ __forceinline__ bool tick_group_body(const DevConst& c, const int gi_
         if (rollout_frame >= 0 && !deferred) store_feedback(c, state_rw + gi, o, s.w);
     }
     STAMP(5);                                         // stores issued
+    STAMP_WHERE;
     return deferred && valid;
 }
 
@@ -477,21 +478,51 @@ template <int SW> __device__ __forceinline__ int slot_instance(const DevConst& c
 // Front end of the per-tick kernels: where this wavefront stands -- its lane, its index in the workgroup and in the launch (through the
 // virtual block where a sweep is bound).  The wavefront holds the launch slots wave * IPW .. + IPW - 1, lane / LPI picks the group's.
 struct QuadFront { int lane, wv, wave; };
-template <int SW> __device__ __forceinline__ QuadFront quad_front(const DevConst& c)
+template <int SW, int WPG> __device__ __forceinline__ QuadFront quad_front(const DevConst& c)
 {
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int blk = (SW && c.order) ? sweep_vblock(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-    return (QuadFront){(int)(threadIdx.x & 63), wv, blk * ISMPC_QUAD_WAVES + wv};
+    return (QuadFront){(int)(threadIdx.x & 63), wv, blk * WPG + wv};
+}
+// Wavefronts per workgroup of the per-tick lane-group kernels, per shape (RESIDENT: ismpc_tick_quad_inline, whose batch is resident at once;
+// otherwise ismpc_tick_quad and ismpc_tick_quad_one); quad_launch() sizes grid and block from the same function.  The rollout, the fallback
+// launch, the affine and the dense kernels keep ISMPC_QUAD_WAVES.
+// Why it matters: LDS is released when the LAST wavefront of a workgroup ends and a workgroup starts only when all its wave slots are free,
+// while wave lifetimes differ (the knapsack loop runs in lockstep over a wavefront's instances: 6.6 us at p10, 10.8 at p90).  At R = 13,
+// 8 lanes a workgroup of four holds 53 248 B, so a CU's 160 KB admit three of them where registers admit two: a half-finished workgroup
+// holds slots nothing can start in.  Measured, one box, the builds alternated, five runs each (10^9 ticks/s; width 4 | 2 | 1):
+//   <13, 8> ismpc_tick_quad_one, 65 536 instances  1.464-1.519 | 1.518-1.557 | 1.560-1.597   (kernel 46.9 | 44.7 | 43.6 us)
+//   <13, 8> ismpc_tick_quad_one, 32 768            1.266-1.310 | 1.305-1.316 | 1.312-1.346
+//   <13, 8> ismpc_tick_quad (64-set sweep, 65 536) 0.978-1.014 | 1.018-1.030 | 1.034-1.044
+//   <13, 8> ismpc_tick_quad_inline, 16 384         1.022-1.049 | 0.987-1.005 | 1.020-1.072   (a tie: stays 4)
+//   <7, 16> ismpc_tick_quad_inline, 8 192          0.707-0.728 | 0.719-0.731 | 0.700-0.706   (eight runs at 4 and 2: overlapping, stays 4)
+// Slot timeline of the 65 536 launch (scripts/slot_timeline.py), width 4 -> 1: refill gaps 11.9 % -> 5.5 % of the slot time (p50 of a gap
+// 1.8 -> 0.76 us), tail 16 % both; SQ_WAVE_CYCLES over slot cycles 0.78 -> 0.85, SQ_INSTS_VALU per wavefront 1 902 both.
+// A shape's width moves only where every run of the candidate beat every run of width 4 on that shape's bench leg; R = 8 and 16 at 8
+// lanes, R = 8 at 16 lanes, the non-resident 16-lane kernels and the multi-plan instantiations (SW = 2) have no leg and stay 4 (at width 1
+// ismpc_tick_quad_one<13, 8, 2, 2> would also move from 255 to 256 VGPRs and from 10 to 8 spilled ones; no other kernel's registers move).
+// -DISMPC_WPG_8LANE=n (R = 8, 13, 16 at 8 lanes) and -DISMPC_WPG_16LANE=n (R = 7, 8 at 16 lanes) set all three kernels of those shapes
+// for A/B builds (build.build(out=..., flags=...), loaded through ISMPC_LIB; scripts/wg_sweep.sh).
+template <int R, int LPI, bool RESIDENT = false, int SW = 0> constexpr int tick_wpg()
+{
+#ifdef ISMPC_WPG_8LANE
+    if (LPI == 8) return ISMPC_WPG_8LANE;
+#endif
+#ifdef ISMPC_WPG_16LANE
+    if (LPI == 16 && R >= 7) return ISMPC_WPG_16LANE;
+#endif
+    if (LPI == 8 && R == 13 && !RESIDENT && SW != 2) return 1;
+    return ISMPC_QUAD_WAVES;
 }
 template <int R, int LPI, int SW = 0>
-__global__ __launch_bounds__(64 * ISMPC_QUAD_WAVES)
+__global__ __launch_bounds__(64 * (tick_wpg<R, LPI, false, SW>()))
 void ismpc_tick_quad(const DevConst c, const ismpc_tick_in* __restrict__ in_ro, ismpc_tick_in* state_rw,
                      ismpc_tick_out* __restrict__ out, double* __restrict__ u_traj, int batch, int rollout_frame,
                      unsigned char* zmark, int launch_id)
 {
     constexpr int IPW = 64 / LPI;                      // instances per wavefront
-    __shared__ double2 lds_mid[ISMPC_QUAD_WAVES][wave_lds_double2<R, LPI>()];
-    const QuadFront f = quad_front<SW>(c);
+    __shared__ double2 lds_mid[tick_wpg<R, LPI, false, SW>()][wave_lds_double2<R, LPI>()];
+    const QuadFront f = quad_front<SW, tick_wpg<R, LPI, false, SW>()>(c);
     if (f.wave * IPW >= batch) return;
     tick_group_body<R, LPI, SW>(c, slot_instance<SW>(c, f.wave * IPW + f.lane / LPI, batch), batch, f.lane, in_ro, state_rw, out, u_traj, rollout_frame,
                                 zmark, launch_id, lds_mid[f.wv], zmark ? zlist_of(zmark, batch) : nullptr);
@@ -500,14 +531,14 @@ void ismpc_tick_quad(const DevConst c, const ismpc_tick_in* __restrict__ in_ro, 
 // Latency variant for small batches (every wavefront resident at once): a wavefront that deferred one of its
 // instances runs the inequality fallback for it right away, with all 64 lanes, so a step is ONE launch.
 template <int R, int LPI, int RW>
-__global__ __launch_bounds__(64 * ISMPC_QUAD_WAVES, 2)      // two wavefronts per SIMD (that is all a batch that takes this kernel has)
+__global__ __launch_bounds__(64 * (tick_wpg<R, LPI, true>()), 2)      // two wavefronts per SIMD (that is all a batch that takes this kernel has)
 void ismpc_tick_quad_inline(const DevConst c, const ismpc_tick_in* __restrict__ in_ro, ismpc_tick_in* state_rw,
                             ismpc_tick_out* __restrict__ out, double* __restrict__ u_traj, int batch, int rollout_frame,
                             unsigned char* zmark, int launch_id, const DevConst* __restrict__ cdev)
 {
     constexpr int IPW = 64 / LPI;
-    __shared__ double2 lds_mid[ISMPC_QUAD_WAVES][wave_lds_double2_fb<R, LPI>()];
-    const QuadFront f = quad_front<0>(c);
+    __shared__ double2 lds_mid[tick_wpg<R, LPI, true>()][wave_lds_double2_fb<R, LPI>()];
+    const QuadFront f = quad_front<0, tick_wpg<R, LPI, true>()>(c);
     if (f.wave * IPW >= batch) return;
     const bool def = tick_group_body<R, LPI>(c, f.wave * IPW + f.lane / LPI, batch, f.lane, in_ro, state_rw, out, u_traj, rollout_frame, zmark, launch_id, lds_mid[f.wv]);
     unsigned long long m = __builtin_amdgcn_ballot_w64(def);
@@ -530,14 +561,14 @@ void ismpc_tick_quad_inline(const DevConst c, const ismpc_tick_in* __restrict__ 
 #endif
 template <int R, int SW> constexpr int one_occ() { return R <= 4 ? (SW ? 3 : 4) : R <= 7 ? 3 : R == 8 ? (SW ? 2 : 3) : R <= 13 ? ISMPC_OCC_R13 : 1; }
 template <int R, int LPI, int RW, int SW>
-__global__ __launch_bounds__(64 * ISMPC_QUAD_WAVES, (one_occ<R, SW>()))
+__global__ __launch_bounds__(64 * (tick_wpg<R, LPI, false, SW>()), (one_occ<R, SW>()))
 void ismpc_tick_quad_one(const DevConst c, const ismpc_tick_in* __restrict__ in_ro, ismpc_tick_in* state_rw,
                          ismpc_tick_out* __restrict__ out, double* __restrict__ u_traj, int batch, int rollout_frame,
                          unsigned char* zmark, int launch_id, const DevConst* __restrict__ cdev)
 {
     constexpr int IPW = 64 / LPI;
-    __shared__ double2 lds_mid[ISMPC_QUAD_WAVES][wave_lds_double2_fb<R, LPI>()];
-    const QuadFront f = quad_front<SW>(c);
+    __shared__ double2 lds_mid[tick_wpg<R, LPI, false, SW>()][wave_lds_double2_fb<R, LPI>()];
+    const QuadFront f = quad_front<SW, tick_wpg<R, LPI, false, SW>()>(c);
     if (f.wave * IPW >= batch) return;
     const bool def = tick_group_body<R, LPI, SW>(c, slot_instance<SW>(c, f.wave * IPW + f.lane / LPI, batch), batch, f.lane, in_ro, state_rw, out, u_traj,
                                                  rollout_frame, zmark, launch_id, lds_mid[f.wv]);

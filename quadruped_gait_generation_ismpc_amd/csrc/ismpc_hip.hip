@@ -186,7 +186,11 @@ constexpr bool has_rollout_quad(int lpi, int sw) { return sw != 1 || lpi == 16; 
 
 // What a launch of a lane-group kernel needs, for launch() and ismpc_rollout_device(): the lanes per instance of pick_layout(), the constants
 // with that layout's affine tables and set records, the order of ismpc_sweep_bind where it applies, and the grid.
-struct QuadLaunch { int lpi, waves; dim3 grid, block; DevConst c; };
+// (width(): grid and block at `wpg` wavefronts per workgroup -- ISMPC_QUAD_WAVES for the rollout, tick_wpg() of the shape for the per-tick kernels)
+struct QuadLaunch {
+    int lpi, waves; dim3 grid, block; DevConst c;
+    void width(int wpg) { grid = dim3((waves + wpg - 1) / wpg); block = dim3(64 * wpg); }
+};
 // (sweep and multi-plan handles: the records that go with the lane layout; a plain handle has none)
 const DevConst* sets_for(const ismpc_handle* h, int lpi)
 {
@@ -195,8 +199,8 @@ const DevConst* sets_for(const ismpc_handle* h, int lpi)
 QuadLaunch quad_launch(const ismpc_handle* h, int batch, bool per_tick)
 {
     const LaneLayout lay = pick_layout(h, batch, per_tick);
-    const int waves = (batch * lay.lpi + 63) / 64;
-    QuadLaunch q{lay.lpi, waves, dim3((waves + ISMPC_QUAD_WAVES - 1) / ISMPC_QUAD_WAVES), dim3(64 * ISMPC_QUAD_WAVES), h->c};
+    QuadLaunch q{lay.lpi, (batch * lay.lpi + 63) / 64, dim3(), dim3(), h->c};
+    q.width(ISMPC_QUAD_WAVES);
     q.c.vqT = lay.vqT; q.c.tzgT = lay.tzgT;
     q.c.sets = sets_for(h, lay.lpi);
     // (ismpc_sweep_bind; per-tick launches of the bound batch only, and never a plain handle: ismpc_sweep_bind refuses it)
@@ -256,7 +260,7 @@ int launch(ismpc_handle* h, int batch, const ismpc_tick_in* in, ismpc_tick_in* s
         auto fallback = [&](auto RR, auto SW) { tick(ismpc_tick_affine_fallback<RR, SW>, fgrid, block, 0, h->c, zm, lid); };      // (the handle's own constants, not the lane-group launch's: one instance per wavefront)
         // default for N <= 128: several instances per wavefront (ismpc_tick_quad); ISMPC_PATH=wave keeps one per wavefront
         if (h->quad_path && h->c.N <= 128) {
-            const QuadLaunch q = quad_launch(h, batch, rollout_frame < 0);      // (a closed loop driven from the host keeps the in-kernel loop's layout: same bytes)
+            QuadLaunch q = quad_launch(h, batch, rollout_frame < 0);      // (a closed loop driven from the host keeps the in-kernel loop's layout: same bytes)
             // every wavefront resident at once (<= 2 per SIMD) and a fallback to run: one launch that handles deferred instances itself (plain handles: the
             // resident kernel has no SW instantiations)
             const bool resident = form_bits(h) == 0 && zm && h->one_launch >= 1 && h->cus > 0 && q.waves <= 8 * h->cus;
@@ -269,6 +273,7 @@ int launch(ismpc_handle* h, int batch, const ismpc_tick_in* in, ismpc_tick_in* s
                 constexpr int sw = decltype(SW)::value;
                 return quad_shape(h->c.N, q.lpi, [&](auto RR, auto LL, auto RW_) {
                     if constexpr (has_tick_quad(LL, sw)) {
+                        q.width(resident ? tick_wpg<RR, LL, true>() : tick_wpg<RR, LL, false, sw>());      // (the workgroup of the kernel launched below)
                         if (resident) {
                             tick(ismpc_tick_quad_inline<RR, LL, RW_>, q.grid, q.block, 0, q.c, zm, lid, h->c_dev);
                             note(ISMPC_KERNEL_QUAD_INLINE, LL, RR, RW_, 1, q.c.order != nullptr);
