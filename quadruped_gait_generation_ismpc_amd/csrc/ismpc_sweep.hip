@@ -114,13 +114,7 @@ __global__ __launch_bounds__(256) void sweep_gemm(const double* __restrict__ A, 
             }
 }
 
-// R = alpha_k U - T (the residual of H M1 = alpha U, T = H M1 from the MFMA product) and M1 += D (the correction Hinv R)
-__global__ __launch_bounds__(256) void sweep_residual(const double* __restrict__ par, const double* __restrict__ U, double* __restrict__ T, size_t smat, int NG)
-{
-    const double alpha = 1.0 / par[blockIdx.y * PAR + 0];
-    double* Ts = T + (size_t)blockIdx.y * smat;
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < NG * NG; e += gridDim.x * blockDim.x) Ts[e] = fma(alpha, U[e], -Ts[e]);
-}
+// M += D (the Newton correction X (I - H X) of sweep_residual_dd)
 __global__ __launch_bounds__(256) void sweep_accumulate(double* __restrict__ M, const double* __restrict__ D, size_t smat, int NG)
 {
     double* Ms = M + (size_t)blockIdx.y * smat; const double* Ds = D + (size_t)blockIdx.y * smat;
@@ -147,26 +141,73 @@ __global__ __launch_bounds__(256) void sweep_transpose_nt(const double* __restri
     }
 }
 
+// ---- double-double (TwoSum / TwoProduct) for the few sums whose cancellation the host's long double keeps and plain fp64 loses:
+// the residuals I - H X and f - H h, the right-hand sides f, and the running sums of S_bar_z
+struct DD { double hi, lo; };
+__device__ __forceinline__ void dd_add(DD& a, double b)
+{
+    const double s = a.hi + b, bb = s - a.hi, e = (a.hi - (s - bb)) + (b - bb);
+    a.lo += e; const double t = s + a.lo; a.lo -= (t - s); a.hi = t;
+}
+__device__ __forceinline__ void dd_add(DD& a, const DD& b) { dd_add(a, b.hi); a.lo += b.lo; const double t = a.hi + a.lo; a.lo -= (t - a.hi); a.hi = t; }
+// (contract(off): the rounded product must be ONE value.  Left to fuse x * y into the additions that use it, the compiler fuses it into
+// some and not others, and the error term of TwoProduct then belongs to a product that half of TwoSum never saw rounded)
+__device__ __forceinline__ void dd_submul(DD& a, double x, double y)         // a -= x y, the product exact
+{
+#pragma clang fp contract(off)
+    const double b = -(x * y), eb = fma(-x, y, -b);
+    const double s = a.hi + b, bb = s - a.hi, e = (a.hi - (s - bb)) + (b - bb);
+    a.lo += e + eb; const double t = s + a.lo; a.lo -= (t - s); a.hi = t;
+}
+__device__ __forceinline__ DD dd_mul(const DD& a, double b)
+{
+#pragma clang fp contract(off)
+    const double p = a.hi * b, e = fma(a.hi, b, -p) + a.lo * b, t = p + e;
+    return DD{t, e - (t - p)};
+}
+
+// T = I - H X on the N x N block, zero on the padding (where H and X are the identity).  A converged Newton-Schulz iterate carries
+// cond(H) eps of rounding noise, and a residual summed in fp64 cannot see below that; from this one the step X += X T leaves the
+// inverse of the fp64 Hessian to an ulp, so that every table derived from it carries the rounding of H's entries and no more.
+__global__ __launch_bounds__(256) void sweep_residual_dd(const double* __restrict__ H, const double* __restrict__ X, double* __restrict__ T, size_t smat, int N, int NG)
+{
+    const double* Hs = H + (size_t)blockIdx.y * smat; const double* Xs = X + (size_t)blockIdx.y * smat; double* Ts = T + (size_t)blockIdx.y * smat;
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < NG * NG; e += gridDim.x * blockDim.x) {
+        const int i = e / NG, j = e - i * NG;
+        double r = 0.0;
+        if (i < N && j < N) {
+            DD acc = {(i == j) ? 1.0 : 0.0, 0.0};
+            for (int k = 0; k < N; ++k) dd_submul(acc, Hs[(size_t)i * NG + k], Xs[(size_t)k * NG + j]);
+            r = acc.hi + acc.lo;
+        }
+        Ts[e] = r;
+    }
+}
+
 // ---- h_b = Hinv f_b, b = 0, a, b: f = f0 + z fa + zdot fb (MPCSolver.cpp:259; ismpc_tables.cpp "affine tables")
 __global__ __launch_bounds__(256) void sweep_hvec(const double* __restrict__ par, const double* __restrict__ Hinv, const double* __restrict__ H, size_t smat,
                                                   double* __restrict__ hvec, int N, int NG, double dt)
 {
-    __shared__ double f[3][256], hcur[3][256], res[3][256];
+    __shared__ double f[3][256], flo[3][256], hcur[3][256], res[3][256];
     const int set = blockIdx.x, tid = threadIdx.x;
     const double mass = par[set * PAR + 0], q_p = par[set * PAR + 1], q_u = par[set * PAR + 2], q_v = par[set * PAR + 3], h_des = par[set * PAR + 4], g = par[set * PAR + 7];
     const double cs = dt * dt / mass, cv = dt / mass;
     if (tid < 3) {
-        // S_bar_z' r (o[i] = cs sum_{k>i} (k-i) r_k) and S_bar_z_v' r (o[i] = cv sum_{k>i} r_k) as suffix sums
-        double t1 = 0.0, t2 = 0.0, acc = 0.0;
+        // S_bar_z' r (o[i] = cs sum_{k>i} (k-i) r_k) and S_bar_z_v' r (o[i] = cv sum_{k>i} r_k) as suffix sums, in double-double: h = Hinv f
+        // cancels (|Hinv||f| >> |h|), so an fp64 f would put cond(H) eps of noise into h whatever the solve does
+        DD t1 = {0.0, 0.0}, t2 = {0.0, 0.0}, acc = {0.0, 0.0};
+        const double gz = g * dt * dt, gv = g * dt;
         for (int i = N - 1; i >= 0; --i) {
             const double k = (double)i;
-            const double tgz = -g * dt * dt * (k * (k + 1.0) / 2.0), tgv = -g * dt * k, tvec = (k + 1.0) * dt;
-            double rp, rv;                                                   // position row / velocity row right-hand sides
-            if (tid == 0) { rp = tgz - h_des; rv = tgv; } else if (tid == 1) { rp = 1.0; rv = 0.0; } else { rp = tvec; rv = 1.0; }
-            double v = q_p * (cs * t2) + q_v * (cv * acc);
-            if (tid == 0) v -= q_u * mass * g;
-            f[tid][i] = v;
-            t1 += rp; t2 += t1; acc += rv;
+            DD rp, rv;                                                       // position row / velocity row right-hand sides
+            if (tid == 0) { rp = dd_mul(DD{-(k * (k + 1.0) / 2.0), 0.0}, gz); dd_add(rp, -h_des); rv = dd_mul(DD{-k, 0.0}, gv); }
+            else if (tid == 1) { rp = DD{1.0, 0.0}; rv = DD{0.0, 0.0}; }
+            else { rp = dd_mul(DD{k + 1.0, 0.0}, dt); rv = DD{1.0, 0.0}; }
+            DD v = dd_mul(dd_mul(t2, cs), q_p);
+            dd_add(v, dd_mul(dd_mul(acc, cv), q_v));
+            if (tid == 0) { DD w = dd_mul(dd_mul(DD{-q_u, 0.0}, mass), g); dd_add(v, w); }
+            f[tid][i] = v.hi; flo[tid][i] = v.lo;
+            dd_add(t1, rp); dd_add(t2, t1); dd_add(acc, rv);
         }
     }
     __syncthreads();
@@ -178,14 +219,14 @@ __global__ __launch_bounds__(256) void sweep_hvec(const double* __restrict__ par
         hcur[b][i] = s;
     }
     __syncthreads();
-    // two steps of iterative refinement on H h = f: h = X f carries the inverse's own error, amplified by the cancellation in
-    // X f (|X||f| >> |X f|); the corrected h only carries the rounding of the residual
+    // two steps of iterative refinement on H h = f: h = X f carries the rounding of the product, amplified by the cancellation in
+    // X f (|X||f| >> |X f|); with the residual exact (double-double) the correction is the error of h itself, not noise of its size
     for (int step = 0; step < 2; ++step) {
         for (int e = tid; e < 3 * N; e += blockDim.x) {
             const int b = e / N, i = e - b * N;
-            double r = f[b][i];
-            for (int j = 0; j < N; ++j) r = fma(-Hm[(size_t)i * NG + j], hcur[b][j], r);
-            res[b][i] = r;
+            DD r = {f[b][i], flo[b][i]};
+            for (int j = 0; j < N; ++j) dd_submul(r, Hm[(size_t)i * NG + j], hcur[b][j]);
+            res[b][i] = r.hi + r.lo;
         }
         __syncthreads();
         double upd[3] = {0.0, 0.0, 0.0};
@@ -197,16 +238,6 @@ __global__ __launch_bounds__(256) void sweep_hvec(const double* __restrict__ par
     }
     for (int e = tid; e < 3 * N; e += blockDim.x) hvec[((size_t)set * 3 + e / N) * NG + e % N] = hcur[e / N][e % N];
 }
-
-// o[k] = cs sum_{j<k} (k-j) v_j (S_bar_z applied as a double running sum), with the two running sums carried as double-double
-// (TwoSum): the plain recurrence loses digits in sums of N^2/2 terms of mixed sign that the host's long double keeps
-struct DD { double hi, lo; };
-__device__ __forceinline__ void dd_add(DD& a, double b)
-{
-    const double s = a.hi + b, bb = s - a.hi, e = (a.hi - (s - bb)) + (b - bb);
-    a.lo += e; const double t = s + a.lo; a.lo -= (t - s); a.hi = t;
-}
-__device__ __forceinline__ void dd_add(DD& a, const DD& b) { dd_add(a, b.hi); a.lo += b.lo; const double t = a.hi + a.lo; a.lo -= (t - a.hi); a.hi = t; }
 
 // ---- one workgroup per (equality pattern, set): W_p = Hinv[:,E] (Hinv[E,E])^-1 (MPCSolver.cpp:223-243: u_i = 0 on a contiguous
 // range that depends on mpcIter only), u = -(I - W_p E') Hinv f and S u for the three right-hand sides, W_p and S W_p re-strided
@@ -446,15 +477,15 @@ int sweep_build(const ismpc_params* sets, int K, const Tables& t0, const double*
     }
     if (X != o.X0) SW_TRY(hipMemcpyAsync(o.X0, X, (size_t)K * o.s_mat * sizeof(double), hipMemcpyDeviceToDevice, s));
     hipLaunchKernelGGL(sweep_symmetrise, dim3(16, K), dim3(256), 0, s, o.X0, o.s_mat, N, NG);
+    // one more Newton step from the double-double residual: X0 += X0 (I - H X0)
+    hipLaunchKernelGGL(sweep_residual_dd, dim3(NG * NG / 256, K), dim3(256), 0, s, (const double*)o.H, (const double*)o.X0, o.T, o.s_mat, N, NG);
+    hipLaunchKernelGGL((sweep_gemm<1>), ggrid, dim3(256), 0, s, (const double*)o.X0, o.s_mat, (const double*)o.T, o.s_mat, o.X1, o.s_mat, (const double*)o.par, 0, NG, N);
+    hipLaunchKernelGGL(sweep_accumulate, dim3(16, K), dim3(256), 0, s, o.X0, (const double*)o.X1, o.s_mat, NG);
+    hipLaunchKernelGGL(sweep_symmetrise, dim3(16, K), dim3(256), 0, s, o.X0, o.s_mat, N, NG);
     // inequality fallback: hs_k = Hinv S_k', shs_k = S hs_k (ismpc_tables.cpp, last block)
     hipLaunchKernelGGL((sweep_gemm<1>), ggrid, dim3(256), 0, s, (const double*)o.X0, o.s_mat, (const double*)o.U, (size_t)0, o.M1, o.s_mat, (const double*)o.par, 1, NG, N);
-    // one step of iterative refinement on H M1 = alpha U (as for the right-hand sides in sweep_hvec): two more MFMA products
-    hipLaunchKernelGGL((sweep_gemm<1>), ggrid, dim3(256), 0, s, (const double*)o.H, o.s_mat, (const double*)o.M1, o.s_mat, o.T, o.s_mat, (const double*)o.par, 0, NG, N);
-    hipLaunchKernelGGL(sweep_residual, dim3(16, K), dim3(256), 0, s, (const double*)o.par, (const double*)o.U, o.T, o.s_mat, NG);
-    hipLaunchKernelGGL((sweep_gemm<1>), ggrid, dim3(256), 0, s, (const double*)o.X0, o.s_mat, (const double*)o.T, o.s_mat, o.X1, o.s_mat, (const double*)o.par, 0, NG, N);
-    hipLaunchKernelGGL(sweep_accumulate, dim3(16, K), dim3(256), 0, s, o.M1, (const double*)o.X1, o.s_mat, NG);
     hipLaunchKernelGGL((sweep_gemm<2>), ggrid, dim3(256), 0, s, (const double*)o.Ut, (size_t)0, (const double*)o.M1, o.s_mat, o.SHSt, o.s_HS, (const double*)o.par, 1, NG, N);
-    launches += 4;
+    launches += 3;
     hipLaunchKernelGGL(sweep_transpose_nt, dim3(16, K), dim3(256), 0, s, (const double*)o.M1, o.s_mat, o.HSt, o.s_HS, N, NG);
     if (!t0.flat)
         hipLaunchKernelGGL(sweep_du, dim3(t0.nmid, K), dim3(256), 0, s, (const double*)o.par, midz_dev, t0.nmid, (const double*)o.HSt, o.s_HS, o.dU, o.SdU, o.s_dU, N, dt);
@@ -477,7 +508,7 @@ int sweep_build(const ismpc_params* sets, int K, const Tables& t0, const double*
     o.max_residual = 0.0;
     for (int k = 0; k < K; ++k) {
         // a converged iterate leaves cond(H) x (relative error of X ~ cond eps): far below 1e-3 for any set the affine tables make sense for; an
-        // iteration that ran out of budget, or a Hessian that is not positive definite, leaves O(1) or NaN.  (Accuracy is cond(H) eps, as for
+        // iteration that ran out of budget, or a Hessian that is not positive definite, leaves O(1) or NaN.  (Accuracy is cond(H) eps of H's own entries, as for
         // any inverse in fp64: ismpc_sweep_verify_tables measures it against the long-double host build.)
         if (!(resid[k] <= 1e-3)) {
             err = "parameter set " + std::to_string(k) + ": the vertical Hessian could not be inverted (not positive definite, or conditioned beyond the "

@@ -7,7 +7,8 @@
 //   H_k            closed form of the Toeplitz products (sweep_init)
 //   H_k^-1         Newton-Schulz  X <- X (2I - H X)  from X0 = I / bound(|H|_inf): nothing but dense N x N x N products, batched
 //                  over the sets on v_mfma_f64_16x16x4_f64 with LDS-staged 64 x 16 / 16 x 64 panels (sweep_gemm).  Quadratic
-//                  convergence, self-correcting: the limit is accurate to cond(H) eps, as a Cholesky inverse is.
+//                  convergence, self-correcting: the limit is accurate to cond(H) eps, as a Cholesky inverse is.  One last step
+//                  from a double-double residual (sweep_residual_dd) takes that noise out: what is left is the rounding of H's entries.
 //   Hinv S', S Hinv S'   the two N x N x N products of the inequality fallback -- the same MFMA kernel
 //   per equality pattern: W_p = Hinv[:,E] (Hinv[E,E])^-1, the affine tables u = -(I - W_p E')Hinv f, S u  (sweep_patterns: small,
 //                  VALU + LDS), lane-group layouts (sweep_layout), anticipative tails per eta_k (sweep_tail)

@@ -36,7 +36,7 @@ def sweep64(q):
 def test_device_built_tables_match_the_long_double_host_build(q, sweep64):
     s, ps = sweep64
     info = s.sweep_info()
-    assert info["n_sets"] == 64 and info["newton_iterations"] >= 10 and info["mfma_gemm_launches"] == 2 * info["newton_iterations"] + 4
+    assert info["n_sets"] == 64 and info["newton_iterations"] >= 10 and info["mfma_gemm_launches"] == 2 * info["newton_iterations"] + 3
     worst = {}
     for k in range(64):
         e = s.sweep_verify_tables(k)

@@ -54,7 +54,7 @@ def stairs_plan(S=35, F=10):
     return ftsp
 
 
-@pytest.mark.parametrize("N", [37, 50, 100, 200])
+@pytest.mark.parametrize("N", [37, 50, 100, 200, 1, 2, 8, 65, 129, 256])
 def test_hessian_inverse(probe, N, built_libs):
     p = O.default_params(N)
     h = build(probe, p, O.reference_plan())
@@ -66,7 +66,7 @@ def test_hessian_inverse(probe, N, built_libs):
     probe.probe_free(h)
 
 
-@pytest.mark.parametrize("N", [37, 50, 100])
+@pytest.mark.parametrize("N", [37, 50, 100, 1, 8, 65, 128])
 def test_equality_patterns_match_reference_loop(probe, N, built_libs):
     """MPCSolver.cpp:223-243 transcribed literally vs. the contiguous ranges of the tables."""
     S, F = 35, 10
@@ -132,11 +132,17 @@ def test_tail_table(probe, built_libs):
     probe.probe_free(h)
 
 
-@pytest.mark.parametrize("N,lpi,R", [(37, 8, 8), (100, 8, 13), (100, 16, 7), (100, 32, 4), (128, 8, 16)])
+@pytest.mark.parametrize("N,lpi,R", [(37, 8, 8), (100, 8, 13), (100, 16, 7), (100, 32, 4), (128, 8, 16),
+                                     (1, 32, 4), (9, 8, 8), (65, 8, 13), (104, 8, 13), (105, 8, 16), (65, 16, 7), (112, 16, 7), (113, 16, 8), (65, 32, 4)])
 def test_lane_group_layout_is_the_affine_tables_restrided(probe, N, lpi, R, built_libs):
     """lane_group_tables(): lane li of a group holds the samples li*R .. li*R + R - 1, element for element out of vtab / tz / tg.
     The shapes are those of tests/test_gpu_dispatch_parity.py at which li*R + r runs past N (into the zero padding of vtab) or reaches
-    the largest sample index, 127."""
+    the largest sample index, 127; and the shapes on both sides of every R switch, N below the lane count and one live lane in the second row.
+    Padded entries (li*R + r >= N) are exactly 0.0 in every table.  That is what tick_group_core (csrc/ismpc_b_group.hpp) assumes of a
+    padded sample instead of masking it: u = su = 0 from vqT, so lambda = (g + u / m - g) / zpos is 0 -- provided zpos = z0 + tz zd0 + tg is
+    the instance's own finite height, i.e. tz = tg = 0 too (a non-finite zpos would give 0 * inf = NaN, which the lambda gate lets through) --
+    hence A_n = I in the suffix scan and a_n = 0 in the knapsack counts (tau |a_n| >= h is false even at tau = inf).  Only the min / max of
+    S u, the midpoints and the u_traj stores carry an explicit n < N."""
     NT = 256
     h = build(probe, O.default_params(N), O.reference_plan())
     npp = probe.probe_npat(h) + 1                    # every equality pattern and "no equalities"
@@ -154,4 +160,9 @@ def test_lane_group_layout_is_the_affine_tables_restrided(probe, N, lpi, R, buil
             for j in range(2):
                 assert np.array_equal(vqT[p, :, k, :, j], vtab[p, 2 * k + j][n]), (p, k, j)
     assert np.array_equal(tzgT[:, :, 0], tz[n]) and np.array_equal(tzgT[:, :, 1], tg[n])
+    pad = n >= N
+    assert pad.sum() == lpi * R - N
+    vq = vqT.transpose(0, 2, 4, 1, 3)                                            # [pattern, k, j, r, li]
+    assert np.all(vq[..., pad] == 0.0) and np.all(tzgT[pad] == 0.0)              # (== 0.0 is false for NaN: finite, and zero)
+    assert np.isfinite(vqT).all() and np.isfinite(tzgT).all() and np.abs(vq[..., ~pad]).max() > 0 and (tzgT[~pad][:, 0] > 0).all()
     probe.probe_free(h)
