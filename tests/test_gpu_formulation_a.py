@@ -230,8 +230,9 @@ def test_foot_files_from_device_rollout(FA, name, tmp_path):
                                             ("walk", dict(C=60, P=120, F=3))])                 # short horizon (RL=2 with idle lanes)
 @pytest.mark.parametrize("backend", BACKENDS)
 def test_other_horizons_against_oracle(FA, kind_name, over, backend):
-    """F_A = ceil(C/step)+1 footsteps for long horizons (SURVEY.md 'Index limits'); every (rows-per-lane, F) kernel
-    instantiation that the BASELINE configs reach, nominal closed loop + pushed single ticks, against the oracle."""
+    """F_A = ceil(C/step)+1 footsteps for long horizons (SURVEY.md 'Index limits'); the (rows-per-lane, F) kernel
+    instantiations that the BASELINE configs reach, nominal closed loop + pushed single ticks, against the oracle.
+    Every other instantiation, and the horizons next to a change of rows per lane, are in tests/test_gpu_formulation_a_edges.py."""
     _closed_loop_and_pushes_against_oracle(FA, kind_name, over, backend)
 
 
