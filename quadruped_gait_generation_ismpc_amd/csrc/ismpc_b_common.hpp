@@ -142,11 +142,18 @@ template <int SW> __device__ __forceinline__ int record_index(const DevConst& c,
     } else return (reserved >= 0 && reserved < c.nsets) ? reserved : -1;
 }
 // 0 = run the tick, else the pass-through status (MPCSolver.cpp:214; index range of :259,381)
+// Both cold cases are uniform over the launch: the remainder sequence sits behind a scalar branch (x % 1 = 0), and with BRANCH_DIV so does the
+// division sequence at mpc_dt = control_dt -- the empty asm keeps it there, a plain conditional is if-converted back into divide-and-select.
+// BRANCH_DIV is the lane-group kernels' alone: in the affine and dense kernels the split block costs registers (ismpc_tick_affine<2, 2>: 55 -> 74
+// VGPRs, eight wavefronts per SIMD -> six), and they are not bound by the instructions they issue.
+template <bool BRANCH_DIV = false>
 __device__ __forceinline__ int gate_tick(const DevConst& c, const Walk& w, int& idx)
 {
     idx = 0;
-    if ((w.ctl % c.tick_divisor) != 0) return ISMPC_ST_TICK_SKIPPED;
-    const double t = (c.sim_div == 1.0) ? w.sim : w.sim / c.sim_div;
+    if (c.tick_divisor != 1 && (w.ctl % c.tick_divisor) != 0) return ISMPC_ST_TICK_SKIPPED;
+    double t = w.sim;
+    if constexpr (BRANCH_DIV) { if (c.sim_div != 1.0) { t = w.sim / c.sim_div; asm volatile("" : "+v"(t)); } }
+    else t = (c.sim_div == 1.0) ? w.sim : w.sim / c.sim_div;
     if (!(t > -1.0) || !(t < 2.0e9)) return ISMPC_ST_BAD_INDEX;
     idx = (int)t;
     if (idx < 0 || idx + 2 * c.N > c.nmid || w.mpc < 0) return ISMPC_ST_BAD_INDEX;

@@ -169,6 +169,17 @@ template <int R, int LPI> constexpr int wave_lds_double2_fb() { return wave_lds_
 // which masks nothing (keep is not read) and compiles to the loop it always had: it sets one simulation time for its whole batch, so its
 // wavefronts hold one gait phase, and both a flight test and a parking mask (valid && alive) measured slower there
 // (scripts/bench_rollout.py, -1 to -3 %).
+// Horizon padding (LPI R slots for N samples; at N = 100, R = 13 only lane 7 owns padded ones, but every slot of every lane paid for the masks):
+// harmless by data wherever that changes no bit -- the bound check on S u without a mask when zlo <= 0 <= zhi in the whole wavefront (a padded
+// su is exactly 0), the midpoint sums without selects (a padded a_n is exactly +-0), the midpoint window without a clamp (zero slack behind the
+// tables), r < N - n0 where a mask stays, and gate_tick's remainder and division behind uniform branches.  Records, u_traj and rollouts hash equal
+// to the parent's on every case of DESIGN section 5.  Measured, one box, builds alternated round-robin, five runs each, 65 536 instances
+// (10^9 ticks/s | isolated kernel us): parent 1.560-1.595 | 43.7-46.2 (one run 41.0); this 1.603-1.658 | 42.8-43.0 (one 39.7).  Each cut alone
+// against the parent is inside the parent's spread (bound check 1.547-1.596, midpoints 1.591-1.615, clamp 1.573-1.600, gate 1.564-1.591); what
+// decided is the set with one cut left out against the whole set (1.619-1.666 | 42.4-42.9): without the bound check 1.586-1.611 | 43.4-44.3,
+// without the midpoint cut 1.583-1.650 | 43.3-44.2, without the clamp cut 1.577-1.631 | 42.6-43.0, without the gate's 1.593-1.631 | 43.1-43.6.
+// Dropped: dt_n of a slot from a per-layout table instead of the select (a new table, upload and DevConst field; -26 selects, +13 loads per
+// lane): the whole set above is WITH it, this build without -- a tie on both figures, so the select stays.
 template <int R, int LPI, int SW = 0, bool MF = true>
 __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lane, const QState& s, QOut& o, double* __restrict__ u_traj_inst,
                                                 double2* __restrict__ lds_wave, const bool keep)
@@ -188,11 +199,16 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
     const double p_dt_over_mass = SW ? P->dt_over_mass : c.dt_over_mass, p_h_des = SW ? P->h_des : c.h_des;
     const double* p_midxy = SW == 2 ? P->midxy : c.midxy;
     int idx;
-    const int gate_status = gate_tick(c, w, idx) | ((SW && s.ps < 0) ? ISMPC_ST_BAD_INDEX : 0);     // group-uniform; a gated group runs the arithmetic on idx = 0 and drops it
+    const int gate_status = gate_tick<MF>(c, w, idx) | ((SW && s.ps < 0) ? ISMPC_ST_BAD_INDEX : 0);     // group-uniform; a gated group runs the arithmetic on idx = 0 and drops it
     int status = gate_status;
     const bool run = gate_status == 0;
     if (!run) idx = 0;
     const int n0 = li * R;                            // this lane owns samples n0 .. n0+R-1 (tables are zero past N)
+    const int nv = N - n0;                            // ... of which slots r < nv are samples of the horizon (the others are padding)
+    // MF = false (the rollout) keeps every mask, the clamp and the compares as they were: with them gone scripts/bench_rollout.py lost 1.6 % at
+    // 65 536 instances without a trajectory (1.731-1.736 -> 1.701-1.708e9 ticks/s, three alternations), and that kernel is kept only if it does not lose
+    constexpr bool LEAN = MF;
+    auto in_horizon = [&](int r) { return LEAN ? r < nv : n0 + r < N; };
     STAMP_DECL;
     STAMP(1);                                         // the record has arrived (gate_tick consumed it)
 
@@ -202,19 +218,36 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
     // midpoint window [idx, idx + LPI R) of this instance -> LDS, coalesced (consumed after the scan; MPCSolver.cpp:328-338,388-389)
     constexpr int MIDM = midm<R>();
     double2* Lm = lds_wave + (lane / LPI) * (LPI * MIDM);
+    // No clamp at the end of the table: the gate admits idx + 2 N <= nmid and the window reads up to idx + LPI R - 1 <= nmid - 2 N + 127, which
+    // every midxy allocation covers with MIDXY_SLACK zero entries behind its last plan (ismpc_hip.hip).  Inside a multi-plan slab the read runs
+    // into the next plan's midpoints instead: finite values in padded slots, which the sums below multiply by an exact zero.
+    const double2* Mw = reinterpret_cast<const double2*>(p_midxy) + (unsigned)(idx + li);
 #pragma unroll
     for (int k = 0; k < R; ++k) {
         const int j = k * LPI + li;
-        Lm[(j / R) * MIDM + (j % R)] = reinterpret_cast<const double2*>(p_midxy)[min(idx + j, c.nmid - 1)];
+        if constexpr (LEAN) Lm[(j / R) * MIDM + (j % R)] = Mw[k * LPI];
+        else Lm[(j / R) * MIDM + (j % R)] = reinterpret_cast<const double2*>(p_midxy)[min(idx + j, c.nmid - 1)];
     }
     double u[R], su[R];
-    double smin = INFINITY, smax = -INFINITY;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const double2 t01 = T[(3 * r) * LPI], t23 = T[(3 * r + 1) * LPI], t45 = T[(3 * r + 2) * LPI];
         u[r] = fma(zd0, t23.x, fma(z0, t01.y, t01.x));
         su[r] = fma(zd0, t45.y, fma(z0, t45.x, t23.y));
-        if (n0 + r < N) { smin = fmin(smin, su[r]); smax = fmax(smax, su[r]); }
+    }
+    // Extrema of S u against the bounds.  A padded slot has su = 0 exactly (its table entries are zero; a non-finite state makes it NaN, which
+    // fmin / fmax pass over), so the extrema over ALL R slots are min(smin, 0) and max(smax, 0): `viol` below is the same decision whenever
+    // zlo_t <= 0 <= zhi_t.  That is tested once per wavefront (the bounds are per instance in a sweep); a wavefront with a bound on the other
+    // side of zero -- or a NaN one -- takes the masked loop.
+    const double zlo_t = p_z_lo - z_tol(p_z_lo), zhi_t = p_z_hi + z_tol(p_z_hi);
+    double smin = INFINITY, smax = -INFINITY;
+    if (LEAN && __builtin_amdgcn_ballot_w64(!(zlo_t <= 0.0 && zhi_t >= 0.0)) == 0ull) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) { smin = fmin(smin, su[r]); smax = fmax(smax, su[r]); }
+    } else {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (in_horizon(r)) { smin = fmin(smin, su[r]); smax = fmax(smax, su[r]); }
     }
     if (!c.flat) {                                      // plans with mid_z != 0 (MPCSolver.cpp:259): per-frame offsets, pattern corrections
         int elo = 0, ne = 0;
@@ -242,10 +275,9 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
             const int n = n0 + r;
             u[r] += du[r]; su[r] += ds[r];
             if (n >= elo && n < elo + ne) u[r] = 0.0;
-            if (n < N) { smin = fmin(smin, su[r]); smax = fmax(smax, su[r]); }
+            if (in_horizon(r)) { smin = fmin(smin, su[r]); smax = fmax(smax, su[r]); }      // (masked: no bench leg runs a plan with heights)
         }
     }
-    const double zlo_t = p_z_lo - z_tol(p_z_lo), zhi_t = p_z_hi + z_tol(p_z_hi);
     const bool viol = smin < zlo_t || smax > zhi_t;                                                // MPCSolver.cpp:158-160, beyond rounding
     const unsigned long long vmask = __builtin_amdgcn_ballot_w64(viol);
     const bool deferred = run && (((vmask >> (lane & (64 - LPI))) & ((1ull << LPI) - 1ull)) != 0ull);
@@ -264,7 +296,7 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
             const double lam = (c.g + zacc) * frcp(zpos);
             if (r == 0) lam0_l = lam;
             le_[r] = (lam < c.gate) ? 0.0 : lam;
-            const double dtn = (n0 + r < N) ? dt : 0.0;
+            const double dtn = in_horizon(r) ? dt : 0.0;
             wv_[r] = le_[r] * dtn * dtn;
             s1[r] = dtn;                                  // dt_n for now
             big = big || (wv_[r] > 0.25);
@@ -317,10 +349,12 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();          // the staged window is complete
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const int n = n0 + r;
+        // No mask on a padded slot: its a[r] is +-0 exactly (ch1 = s2 = 0 where dt_n = 0) and what the window holds there is finite (the
+        // plan's later midpoints, the next plan's, or the zero slack), so fma(+-0, m, s) = s -- s starts at +0 and a sum that is never -0
+        // stays what it was.  Where a[r] is NaN (a non-finite state) the masked form fma(NaN, 0, s) was NaN just as well.
         const double2 mq = Lm[li * MIDM + r];
-        const double mx = (n < N) ? mq.x : 0.0, my = (n < N) ? mq.y : 0.0;
-        if (r == 0) { mx0 = mx; my0 = my; }
+        const double mx = (LEAN || in_horizon(r)) ? mq.x : 0.0, my = (LEAN || in_horizon(r)) ? mq.y : 0.0;
+        if (r == 0) { mx0 = mx; my0 = my; }               // (read in lane 0 only, whose first sample is inside every horizon)
         q0 = fma(a[r], a[r], q0); s_ax = fma(a[r], mx, s_ax); s_ay = fma(a[r], my, s_ay);
     }
     q0 = Grp<LPI>::sum(q0); s_ax = Grp<LPI>::sum(s_ax); s_ay = Grp<LPI>::sum(s_ay);
@@ -409,7 +443,7 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int n = n0 + r;
-            if (n < N) {
+            if (in_horizon(r)) {
                 double vx = 0.0, vy = 0.0;
                 if (stage3) {
                     // (SW = 2: the plan's midpoints from the staged window -- the same values, and the pair's record need not stay live)

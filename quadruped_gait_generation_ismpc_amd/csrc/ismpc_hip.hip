@@ -131,11 +131,16 @@ constexpr int LPI32_BATCH = 2048;
 // the instances (round 3, one box: 65 536 instances 1.30-1.35 -> 1.41-1.44e9 ticks/s, 32 768 1.18 -> 1.24e9, 16 384 0.94 -> 1.03e9;
 // 8 192 level, 1 024 slower)
 constexpr int LPI16_BATCH = 8192;
+// Zero double2 entries behind the last plan of every midxy table.  The lane-group kernels stage the window [idx, idx + LPI R) of an instance
+// without a clamp (tick_group_core); the gate admits idx <= nmid - 2 N, so the largest entry read is nmid - 2 N + LPI R - 1 of the instance's
+// plan -- past the table's end by at most LPI R - 2 N <= 126 entries (N >= 1; LPI R <= 128 in every shape of quad_shape()).
+constexpr size_t MIDXY_SLACK = 128;
 struct LaneLayout { int lpi; const double* vqT; const double* tzgT; };
 // THE shape table: calls f(R, LPI, RW) with the compile-time shape (std::integral_constant arguments) of horizon N at lpi lanes
 // per instance, and returns what f returns.  Every launch of a lane-group kernel and quad_R() go through it.
 template <int R, int LPI, int RW, class F> auto with_shape(F&& f)
 {
+    static_assert((size_t)R * LPI <= MIDXY_SLACK, "the unclamped midpoint window of this shape needs more slack behind the midxy tables");
     return f(std::integral_constant<int, R>{}, std::integral_constant<int, LPI>{}, std::integral_constant<int, RW>{});
 }
 template <class F> auto quad_shape(int N, int lpi, F&& f)
@@ -438,7 +443,7 @@ int upload_tables(ismpc_handle* h, bool all_layouts)
     h->dev_allocs.push_back(pool); c.zpool = static_cast<double*>(pool);
     constexpr int NTq = ismpc::Tables::NT;
     const size_t npp = t.vtab.size() / (6 * (size_t)NTq);
-    std::vector<double> vq(t.vtab.size()), tzg(2 * (size_t)NTq), mxy(2 * t.midx.size());
+    std::vector<double> vq(t.vtab.size()), tzg(2 * (size_t)NTq), mxy(2 * (t.midx.size() + MIDXY_SLACK), 0.0);
     for (size_t pp = 0; pp < npp; ++pp)
         for (int k = 0; k < 6; ++k)
             for (int n = 0; n < NTq; ++n) vq[(pp * NTq + n) * 6 + k] = t.vtab[(pp * 6 + k) * NTq + n];
@@ -464,7 +469,7 @@ int upload_plans(ismpc_handle* h, const ismpc_params& p0, const double* ftsp, Pl
 {
     const int P = h->nplans, rows = h->t.rows; const bool sweep = h->sweep;
     const size_t nm = (size_t)h->t.nmid;
-    std::vector<double> mxy(2 * nm * P), tt((size_t)rows * P), tx(sweep ? 0 : nm * P), ty(sweep ? 0 : nm * P);
+    std::vector<double> mxy(2 * (nm * P + MIDXY_SLACK), 0.0), tt((size_t)rows * P), tx(sweep ? 0 : nm * P), ty(sweep ? 0 : nm * P);
     h->pl_midx.resize(nm * P); h->pl_midy.resize(nm * P);
     for (int p = 0; p < P; ++p) {
         ismpc::PlanTables pt;
