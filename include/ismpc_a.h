@@ -110,7 +110,7 @@ int ismpc_a_plan(const ismpc_a_gait* g, double* foot_plan, double* center);
 int ismpc_a_create(const ismpc_a_params* p, const double* center, int device, ismpc_a_handle** out);
 void ismpc_a_destroy(ismpc_a_handle* h);
 
-/* Optional: size the handle's scratch (copy of the previous state, working-set history) for batches up to max_batch now;
+/* Optional: size the handle's scratch (copy of the previous state, working-set history, the disturbed rollout's records) for batches up to max_batch now;
  * otherwise it grows inside the asynchronous entry points with stream-ordered allocations on the caller's stream. */
 int ismpc_a_reserve(ismpc_a_handle* h, int max_batch);
 
@@ -150,6 +150,61 @@ int ismpc_a_tick_batch_inst_device(ismpc_a_handle* h, int batch, ismpc_a_state* 
                                    const double* push_dev, ismpc_a_out* out_dev, void* stream);
 int ismpc_a_rollout_inst_device(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, const ismpc_a_inst* inst_dev,
                                 int ticks, ismpc_a_out* out_traj_dev, void* stream);
+
+/* DISTURBED closed loop with per-instance summaries: the tick loop of ismpc_a_rollout_device (inst_dev = NULL: the handle's
+ * parameters) or ismpc_a_rollout_inst_device (batch records) -- same working-set history, same behaviour on error ticks: the loop goes
+ * on -- with the three additions of ismpc_rollout_mc_device (ismpc.h).  Works on every handle those two take, in either precision.  One
+ * prologue launch and the solver launch(es) per tick, as there, and one small launch behind the last tick when a summary is asked for.
+ * No swing-foot variant: the call has no feet_dev argument.
+ *
+ * PUSHES.  The scripts' impulsive velocity "bang" (quad_walk_no_plots.m:134-148) as a table: pushes_dev holds n_push entries per
+ * instance, instance-major (entry k of instance i at [i * n_push + k]).  An entry applies at tick t when its tick == t and no earlier
+ * entry of the same instance has a larger tick.  So a table in ascending order applies every entry; several entries with one tick all
+ * apply; an entry behind a larger tick is skipped; a negative tick and a tick >= ticks never apply (INT32_MAX pads unused slots, and
+ * blocks whatever follows it).  The tick's push is the fp64 sum of its applying entries' dv, in table order from 0.0, and is what
+ * ismpc_a_tick_batch_device takes as push_dev: added once to (xd, yd) of the tick's input state, before the QPs.  Ticks count from 0 at
+ * THIS call.  dv is not validated: it is a state like any other.
+ *
+ * TRAJECTORY.  traj_dev is NULL or (ticks / traj_stride) x batch records; tick t is recorded when (t + 1) % traj_stride == 0, in row
+ * (t + 1) / traj_stride - 1.  traj_stride = 1 is ismpc_a_rollout_device's layout.
+ *
+ * SUMMARY.  summary_dev is NULL or batch records, one per instance, over the output records of ALL ticks of the call, recorded or
+ * not.  The extrema are taken with fmax: independent of the order and bit-exact against a host reduction (np.fmax) of the stride-1
+ * trajectory of the same call.  ticks = 0 gives the empty summary: 0, -1, 0, 0, 0, 0, 0, 0, and 0.0 four times.
+ *
+ * With n_push = 0, traj_stride = 1 and summary_dev = NULL the call enqueues the launches of ismpc_a_rollout_device /
+ * ismpc_a_rollout_inst_device (no push buffer reaches the solver): trajectory and final state are byte-identical.  With pushes it is
+ * byte-identical to the caller-driven loop: ismpc_a_set_warm_history(h, 1) on a fresh handle, then `ticks` calls of
+ * ismpc_a_tick_batch[_inst]_device, each given a batch x 2 push array (zeros where nothing applies).
+ * Returns -1 before the device is touched, ismpc_a_last_error naming the argument: null handle, negative batch or ticks,
+ * traj_stride < 1, n_push < 0, n_push > 0 with a null table, batch > 0 with a null state.  The handle-owned scratch (per instance one
+ * output record for ticks that only the summary wants, and the tick's push) grows stream-ordered; ismpc_a_reserve sizes it beforehand. */
+#define ISMPC_A_ST_ERROR_MASK (ISMPC_A_ST_X_INFEASIBLE | ISMPC_A_ST_Y_INFEASIBLE | ISMPC_A_ST_OVERFLOW | ISMPC_A_ST_BAD_INDEX)
+
+typedef struct ismpc_a_push {            /* 24 bytes */
+    int32_t tick;                        /* tick of THIS call, 0 <= tick < ticks */
+    int32_t reserved;                    /* 0 */
+    double  dv[2];                       /* added to (xd, yd) of the tick's input state, before the QPs */
+} ismpc_a_push;
+
+typedef struct ismpc_a_rollout_summary { /* 64 bytes */
+    int32_t status_or;                   /* OR of ismpc_a_out.status over all ticks of the call */
+    int32_t first_error_tick;            /* first tick with status & ISMPC_A_ST_ERROR_MASK; -1: none */
+    int32_t error_ticks;                 /* number of such ticks */
+    int32_t iter_limit_ticks;            /* ticks with ISMPC_A_ST_ITER_LIMIT */
+    int32_t iters_sum_x, iters_sum_y;    /* sum of iters_x / iters_y over the ticks */
+    int32_t max_active_x, max_active_y;  /* max of (active & 0xffff) / (active >> 16) */
+    double  max_abs_vel[2];              /* max |vel_after[k]| (fmax) */
+    double  max_abs_u0[2];               /* max |u0[k]| (fmax) */
+} ismpc_a_rollout_summary;
+
+int ismpc_a_rollout_mc_device(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev,
+                              const ismpc_a_inst* inst_dev,            /* NULL: the handle's parameters; else batch records */
+                              int ticks,
+                              const ismpc_a_push* pushes_dev, int n_push,  /* batch x n_push, instance-major; NULL with n_push = 0 */
+                              int traj_stride, ismpc_a_out* traj_dev,      /* NULL, or (ticks / traj_stride) x batch records */
+                              ismpc_a_rollout_summary* summary_dev,        /* NULL, or batch records */
+                              void* stream);
 
 /* ---- swing-foot re-placement (the scripts' second quadprog) and the trajectory wire format -------------------
  *   ismpc_a_feet_init_device / ismpc_a_tick_feet_batch_device / ismpc_a_rollout_feet_device

@@ -11,7 +11,8 @@
 //   ismpc_host.hpp          device guard, early return on a HIP error, growth of scratch (shared by the three ABIs)
 //   this file               the error string; host geometry (linspace_m, centreline, ismpc_a_plan, ismpc_a_foot_trajectories, the text
 //                           writer); ismpc_a_handle and its run-time knobs; the launch path (ismpc_a_tick_prologue, ismpc_a_bucket_by_F,
-//                           tick_launch, tick_feet, rollout_a); the extern "C" entry points
+//                           tick_launch, tick_feet, rollout_a); the disturbed closed loop (ismpc_a_mc_prologue, ismpc_a_mc_fold,
+//                           ismpc_a_rollout_mc_device); the extern "C" entry points
 //
 // Results are the unique minimiser: validated against the oracle's null-space Goldfarb-Idnani and the
 // reference's qpOASES (tests/).  No CPU fallback.
@@ -93,12 +94,14 @@ struct ismpc_a_handle {
                                                           // half is +2-12 % on every bench leg, three quarters starts to cost balance)
     bool hist_ticks = false, hist_valid = false;           // use it in plain tick calls too / it holds the previous tick of this batch
     int hist_batch = 0; bool hist_off = false;            // ISMPC_A_HISTORY=0: never (A/B)
+    ismpc_a_out* mc = nullptr; int mc_cap = 0;            // disturbed rollouts: per instance an output record for ticks only the summary wants,
+                                                          // then (behind mc_cap records) the tick's push, 2 doubles per instance
     hipStream_t last_stream = nullptr; bool used = false; // stream of the previous launch: scratch that outlives a call is re-allocated only
                                                           // after that stream has drained (ismpc_host::grow_sync, inside ISMPC_GROW_ASYNC)
     std::vector<void*> allocs;                            // allocated once, at ismpc_a_create / ismpc_a_add_plan
     std::vector<double> fsx, fsy;
     // the scratch that is re-allocated as batches grow (ismpc_a_reserve, tick_launch, feet_upload): what ismpc_a_destroy frees besides `allocs`
-    std::array<void*, 6> scratch() const { return {prev, hist, defer_list, order, pre, feet_base}; }
+    std::array<void*, 7> scratch() const { return {prev, hist, defer_list, order, pre, feet_base, mc}; }
 };
 
 namespace {
@@ -176,6 +179,108 @@ __global__ void ismpc_a_tick_prologue(const ismpc_a_state* __restrict__ state, i
         pre[i] = q;
     }
     if (out) { out[i].status = 0; out[i].active = 0; out[i].iters_x = 0; out[i].iters_y = 0; }
+}
+
+// ---- the disturbed closed loop (ismpc_a_rollout_mc_device)
+// What tick t of that loop needs beyond a plain tick's prologue.  Nothing is carried from launch to launch but the summary itself.
+struct McTick {
+    const ismpc_a_push* pushes; int n_push, t;            // the push table (batch x n_push, instance-major) and the tick; NULL: no pushes
+    double* push;                                         // batch x 2, the handle's: what the solver launch of tick t reads as `push`
+    const ismpc_a_out* last; ismpc_a_rollout_summary* summary;   // output records of tick t - 1 (NULL at t = 0), folded into summary (NULL: none)
+};
+constexpr size_t MC_BYTES_PER_INSTANCE = sizeof(ismpc_a_out) + 2 * sizeof(double);   // ismpc_a_handle::mc: a record and a push per instance
+static_assert(sizeof(ismpc_a_out) % 16 == 0, "the pushes behind the records are stored as 16-byte words");
+
+// The summary of no ticks, and one output record (of tick t) folded into a summary.  fmax: NaN-ignoring and independent of the order,
+// so the extrema are np.fmax over the stride-1 trajectory to the bit.
+__device__ __forceinline__ ismpc_a_rollout_summary mc_empty_summary()
+{
+    ismpc_a_rollout_summary s;
+    s.status_or = 0; s.first_error_tick = -1; s.error_ticks = 0; s.iter_limit_ticks = 0;
+    s.iters_sum_x = 0; s.iters_sum_y = 0; s.max_active_x = 0; s.max_active_y = 0;
+    s.max_abs_vel[0] = 0.0; s.max_abs_vel[1] = 0.0; s.max_abs_u0[0] = 0.0; s.max_abs_u0[1] = 0.0;
+    return s;
+}
+__device__ __forceinline__ void mc_fold_record(ismpc_a_rollout_summary& s, const ismpc_a_out& o, int t)
+{
+    s.status_or |= o.status;
+    if (o.status & ISMPC_A_ST_ERROR_MASK) { if (s.first_error_tick < 0) s.first_error_tick = t; ++s.error_ticks; }
+    if (o.status & ISMPC_A_ST_ITER_LIMIT) ++s.iter_limit_ticks;
+    s.iters_sum_x += o.iters_x; s.iters_sum_y += o.iters_y;
+    s.max_active_x = max(s.max_active_x, o.active & 0xffff); s.max_active_y = max(s.max_active_y, o.active >> 16);
+    for (int k = 0; k < 2; ++k) { s.max_abs_vel[k] = fmax(s.max_abs_vel[k], fabs(o.vel_after[k])); s.max_abs_u0[k] = fmax(s.max_abs_u0[k], fabs(o.u0[k])); }
+}
+
+// ismpc_a_tick_prologue for tick t of the disturbed loop, in the same single launch: the snapshot, the counters, the PiPre records and
+// the cleared flags as there, and per instance (a) the output record of tick t - 1 folded into the summary, (b) the tick's push from
+// the instance's table, (c) -- by the host, through `out` -- the trajectory row or the handle's scratch record as the tick's output.
+// `out` and mc.last are the same scratch records when neither tick is recorded: the thread that folds a record clears it afterwards.
+// A thread per instance reads its n_push table entries 24 n_push bytes apart (uncoalesced; n_push is a handful) and its 80-byte record
+// and 64-byte summary as 16-byte words 80 / 64 bytes apart -- a few MB per tick at 16 384 instances, next to a solver launch of milliseconds.
+__global__ void ismpc_a_mc_prologue(const ismpc_a_state* __restrict__ state, ismpc_a_state* __restrict__ prev, ismpc_a_out* out, int batch, int* counters,
+                                    const ismpc_a_inst* __restrict__ inst, ismpc_a::PiPre* __restrict__ pre, double grav, double dt, int C, int P, McTick mc)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 4 && counters) counters[i] = 0;
+    // the snapshot and the PiPre record: ismpc_a_tick_prologue's own statements, kept word for word (that kernel stays as it is)
+    {
+        constexpr int WPR = (int)(sizeof(ismpc_a_state) / 16);
+        const double2* src = reinterpret_cast<const double2*>(state);
+        double2* dst = reinterpret_cast<double2*>(prev);
+        const long long nw = (long long)batch * WPR;
+        for (long long w = i; w < nw; w += (long long)gridDim.x * blockDim.x) dst[w] = src[w];
+    }
+    if (i >= batch) return;
+    if (inst && pre) {
+        const double height = inst[i].height;
+        const double eta = (height > 0) ? sqrt(grav / height) : 1.0;
+        const double lam = exp(-eta * dt);
+        auto ipw = [](double b, int n) { double r = 1.0; while (n > 0) { if (n & 1) r *= b; b *= b; n >>= 1; } return r; };
+        const double lamC = ipw(lam, C), lamP = ipw(lam, P);
+        const double r1 = 1.0 / (1.0 - lam);
+        const double k1c = (1 / eta) * (1 - lam) / (1 - lamC), k2c = dt * 1.0 * lamC;
+        ismpc_a::PiPre q;
+        q.eta = eta; q.lam = lam; q.lamC = lamC; q.lamP = lamP; q.k1c = k1c; q.k2c = k2c;
+        q.A1 = k1c * r1; q.A2 = k1c * k1c / ((1.0 - lam) * (1.0 + lam)); q.B2 = 2.0 * k1c * k2c * r1;
+        q.aa = (q.A2 * ((1.0 - lamC) * (1.0 + lamC)) - q.B2 * (1.0 - lamC)) + (double)C * (k2c * k2c);
+        const double Qf = (inst[i].Qf > 0) ? inst[i].Qf : 1.0;
+        const int step = inst[i].step >= 2 ? inst[i].step : 2, ds = inst[i].ds >= 2 ? inst[i].ds : 2;
+        q.sqQf = sqrt(Qf); q.isqQf = 1.0 / sqrt(Qf); q.iQf = 1.0 / Qf; q.ieta = 1.0 / eta;
+        q.inv_ds = 1.0 / (double)ds; q.inv_dsm1 = 1.0 / (double)(ds - 1); q.rstep = 1.0f / (float)step; q.pad_ = 0;
+        const double ie = 1.0 / lam;
+        q.ch = 0.5 * (ie + lam); q.sh = 0.5 * (ie - lam); q.sh_eta = q.sh / eta;
+        pre[i] = q;
+    }
+    if (mc.summary) {
+        ismpc_a_rollout_summary s = mc_empty_summary();
+        if (mc.last) { s = mc.summary[i]; mc_fold_record(s, mc.last[i], mc.t - 1); }
+        mc.summary[i] = s;
+    }
+    if (mc.push) {
+        // the prefix-maximum form of the cursor rule: an entry applies when its tick is this one and no earlier entry of the table has a
+        // larger tick (ticks outside [0, ticks) are never this one); rebuilt from the table every tick, so no cursor is kept anywhere
+        const ismpc_a_push* tab = mc.pushes + (size_t)i * mc.n_push;
+        double dx = 0.0, dy = 0.0;
+        int top = INT32_MIN;
+        for (int k = 0; k < mc.n_push; ++k) {
+            const int tk = tab[k].tick;
+            if (tk < top) continue;
+            top = tk;
+            if (tk == mc.t) { dx += tab[k].dv[0]; dy += tab[k].dv[1]; }
+        }
+        reinterpret_cast<double2*>(mc.push)[i] = make_double2(dx, dy);
+    }
+    if (out) { out[i].status = 0; out[i].active = 0; out[i].iters_x = 0; out[i].iters_y = 0; }
+}
+
+// After the last tick: its output record into the summary (last == NULL: a call of no ticks, the empty summary).
+__global__ void ismpc_a_mc_fold(const ismpc_a_out* __restrict__ last, ismpc_a_rollout_summary* __restrict__ summary, int batch, int t)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= batch) return;
+    ismpc_a_rollout_summary s = mc_empty_summary();
+    if (last) { s = summary[i]; mc_fold_record(s, last[i], t); }
+    summary[i] = s;
 }
 
 }  // namespace
@@ -442,14 +547,16 @@ int ismpc_a_reserve(ismpc_a_handle* h, int max_batch)
         h->hist_valid = false;
         ISMPC_GROW_SYNC(fail_a, h->hist, h->hist_cap, max_batch, sizeof(unsigned long long) * 16 * (size_t)max_batch);
     }
+    if (max_batch > h->mc_cap) ISMPC_GROW_SYNC(fail_a, h->mc, h->mc_cap, max_batch, MC_BYTES_PER_INSTANCE * (size_t)max_batch);
     return 0;
 }
 
 // The handle's scratch (prev, pre, hist, order, defer_list) outlives the call that allocated it and is used by later calls on
 // whatever stream those pass: it grows through ISMPC_GROW_ASYNC (ismpc_host.hpp), which drains the previous launch's stream first.
 static int tick_launch(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, const ismpc_a_inst* inst_dev, const double* push_dev,
-                       ismpc_a_out* out_dev, void* stream, int history = -1)
+                       ismpc_a_out* out_dev, void* stream, int history = -1, const McTick* mc = nullptr)
 {
+    // mc: a tick of the disturbed closed loop (rollout_mc_a): its prologue in place of the plain one, everything else as always
     if (!h || batch < 0 || (batch > 0 && !state_dev)) return fail_a(-1, "bad argument");
     if (batch == 0) return 0;
     ON_DEVICE_A(h);
@@ -475,8 +582,15 @@ static int tick_launch(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, c
     if (inst_dev && batch > h->pre_cap) {
         ISMPC_GROW_ASYNC(fail_a, h, h->pre, h->pre_cap, batch, sizeof(ismpc_a::PiPre) * (size_t)batch, s);
     }
-    hipLaunchKernelGGL(ismpc_a_tick_prologue, dim3((batch + 255) / 256), dim3(256), 0, s, (const ismpc_a_state*)state_dev, h->prev, out_dev, batch,
-                       (h->use_wave || inst_dev) ? h->work_counter : nullptr, inst_dev, inst_dev ? h->pre : nullptr, h->c.grav, h->c.dt, h->c.C, h->c.P);
+    int* const counters = (h->use_wave || inst_dev) ? h->work_counter : nullptr;
+    ismpc_a::PiPre* const pre = inst_dev ? h->pre : nullptr;
+    if (mc) {
+        hipLaunchKernelGGL(ismpc_a_mc_prologue, dim3((batch + 255) / 256), dim3(256), 0, s, (const ismpc_a_state*)state_dev, h->prev, out_dev, batch,
+                           counters, inst_dev, pre, h->c.grav, h->c.dt, h->c.C, h->c.P, *mc);
+    } else {
+        hipLaunchKernelGGL(ismpc_a_tick_prologue, dim3((batch + 255) / 256), dim3(256), 0, s, (const ismpc_a_state*)state_dev, h->prev, out_dev, batch,
+                           counters, inst_dev, pre, h->c.grav, h->c.dt, h->c.C, h->c.P);
+    }
     if (h->use_wave || inst_dev) {
         // structured solver, one wavefront per QP, 4 per workgroup; persistent grid (ismpc_a_wave.hpp)
         const int rl = (h->c.C + 63) / 64;
@@ -692,6 +806,44 @@ int ismpc_a_rollout_inst_device(ismpc_a_handle* h, int batch, ismpc_a_state* sta
     if (!h || batch < 0 || ticks < 0) return fail_a(-1, "bad argument");
     if (ticks > 0 && batch > 0 && !inst_dev) return fail_a(-1, "null per-instance parameter array");
     return rollout_a(h, batch, state_dev, inst_dev, ticks, out_traj_dev, false, nullptr, stream);
+}
+
+// The disturbed closed loop: rollout_a's loop with ismpc_a_mc_prologue as every tick's prologue and one ismpc_a_mc_fold behind the last
+// tick.  Tick t writes its output records into its trajectory row when it has one, into the handle's scratch records when only the
+// summary wants them, and nowhere otherwise.
+int ismpc_a_rollout_mc_device(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, const ismpc_a_inst* inst_dev, int ticks,
+                              const ismpc_a_push* pushes_dev, int n_push, int traj_stride, ismpc_a_out* traj_dev,
+                              ismpc_a_rollout_summary* summary_dev, void* stream)
+{
+    // (what can be said about the numbers is said first: each message is reachable without a handle, i.e. without a device)
+    if (batch < 0 || ticks < 0) return fail_a(-1, "ismpc_a_rollout_mc_device: negative batch or ticks");
+    if (traj_stride < 1) return fail_a(-1, "ismpc_a_rollout_mc_device: traj_stride must be at least 1");
+    if (n_push < 0) return fail_a(-1, "ismpc_a_rollout_mc_device: negative n_push");
+    if (n_push > 0 && !pushes_dev) return fail_a(-1, "ismpc_a_rollout_mc_device: n_push > 0 with a null push table");
+    if (batch > 0 && !state_dev) return fail_a(-1, "ismpc_a_rollout_mc_device: batch > 0 with a null state");
+    if (!h) return fail_a(-1, "ismpc_a_rollout_mc_device: null handle");
+    if (n_push == 0 && traj_stride == 1 && !summary_dev) return rollout_a(h, batch, state_dev, inst_dev, ticks, traj_dev, false, nullptr, stream);
+    if (batch == 0) return 0;
+    ON_DEVICE_A(h);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ismpc_host::StreamMark<ismpc_a_handle> mark_{h, s};
+    if (batch > h->mc_cap) {                             // stream-ordered growth; ismpc_a_reserve sizes it beforehand
+        ISMPC_GROW_ASYNC(fail_a, h, h->mc, h->mc_cap, batch, MC_BYTES_PER_INSTANCE * (size_t)batch, s);
+    }
+    double* const push = n_push > 0 ? reinterpret_cast<double*>(h->mc + h->mc_cap) : nullptr;
+    ismpc_a_out* last = nullptr;                         // where the previous tick's records are
+    for (int t = 0; t < ticks; ++t) {
+        const bool recorded = traj_dev && (t + 1) % traj_stride == 0;
+        ismpc_a_out* out = recorded ? traj_dev + (size_t)((t + 1) / traj_stride - 1) * batch : (summary_dev ? h->mc : nullptr);
+        const McTick mc{pushes_dev, n_push, t, push, summary_dev ? last : nullptr, summary_dev};
+        if (int rc = tick_launch(h, batch, state_dev, inst_dev, push, out, stream, t == 0 ? 1 : 2, &mc)) return rc;
+        last = out;
+    }
+    if (summary_dev) {
+        hipLaunchKernelGGL(ismpc_a_mc_fold, dim3((batch + 255) / 256), dim3(256), 0, s, (const ismpc_a_out*)last, summary_dev, batch, ticks - 1);
+        HIP_TRY_A(hipGetLastError());
+    }
+    return 0;
 }
 
 int ismpc_a_rollout_feet_device(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, int ticks, ismpc_a_out* out_traj_dev,

@@ -32,6 +32,13 @@ OUT_A = np.dtype([("com_before", "<f8", 2), ("vel_after", "<f8", 2), ("u0", "<f8
                   ("status", "<i4"), ("iters_x", "<i4"), ("iters_y", "<i4"), ("active", "<i4")], align=False)
 INST_A = np.dtype([("height", "<f8"), ("Qf", "<f8"), ("step", "<i4"), ("ds", "<i4"), ("F", "<i4"), ("plan", "<i4")], align=False)
 assert STATE_A.itemsize == 96 and OUT_A.itemsize == 80 and INST_A.itemsize == 32
+# the disturbed closed loop (ismpc_a_rollout_mc_device): one push-table entry, one per-instance summary
+PUSH_A = np.dtype([("tick", "<i4"), ("reserved", "<i4"), ("dv", "<f8", 2)], align=False)
+ROLLOUT_SUMMARY_A = np.dtype([("status_or", "<i4"), ("first_error_tick", "<i4"), ("error_ticks", "<i4"), ("iter_limit_ticks", "<i4"),
+                              ("iters_sum_x", "<i4"), ("iters_sum_y", "<i4"), ("max_active_x", "<i4"), ("max_active_y", "<i4"),
+                              ("max_abs_vel", "<f8", 2), ("max_abs_u0", "<f8", 2)], align=False)
+assert PUSH_A.itemsize == 24 and ROLLOUT_SUMMARY_A.itemsize == 64
+ST_ERROR_MASK_A = ST_X_INFEASIBLE | ST_Y_INFEASIBLE | ST_OVERFLOW | ST_BAD_INDEX      # ISMPC_A_ST_ERROR_MASK = 15
 
 EXPORTS_A = ["ismpc_a_params_default", "ismpc_a_gait_default", "ismpc_a_plan", "ismpc_a_create", "ismpc_a_destroy",
              "ismpc_a_initial_state", "ismpc_a_tick_batch_device", "ismpc_a_rollout_device", "ismpc_a_last_error",
@@ -39,7 +46,7 @@ EXPORTS_A = ["ismpc_a_params_default", "ismpc_a_gait_default", "ismpc_a_plan", "
              "ismpc_a_rollout_feet_device", "ismpc_a_foot_trajectories", "ismpc_a_write_trajectory_txt",
              "ismpc_a_add_plan", "ismpc_a_tick_batch_inst_device", "ismpc_a_rollout_inst_device", "ismpc_a_set_warm_history", "ismpc_a_reserve", "ismpc_a_set_precision",
              "ismpc_a_last_deferred", "ismpc_a_feet_init_inst_device", "ismpc_a_tick_feet_batch_inst_device",
-             "ismpc_a_rollout_feet_inst_device"]
+             "ismpc_a_rollout_feet_inst_device", "ismpc_a_rollout_mc_device"]
 HAVE_F32 = True        # the QP solve also exists in fp32 (GaitGenerator(..., precision="f32"))
 FEET_PAD = 8
 
@@ -76,6 +83,7 @@ def _l():
         lib.ismpc_a_feet_init_inst_device.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp]; lib.ismpc_a_feet_init_inst_device.restype = ci
         lib.ismpc_a_tick_feet_batch_inst_device.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]; lib.ismpc_a_tick_feet_batch_inst_device.restype = ci
         lib.ismpc_a_rollout_feet_inst_device.argtypes = [vp, ci, vp, vp, ci, vp, vp, vp]; lib.ismpc_a_rollout_feet_inst_device.restype = ci
+        lib.ismpc_a_rollout_mc_device.argtypes = [vp, ci, vp, vp, ci, vp, ci, ci, vp, vp, vp]; lib.ismpc_a_rollout_mc_device.restype = ci
         _bound = True
     return lib
 
@@ -180,6 +188,43 @@ class GaitGenerator:
                                          C.c_void_p(traj_ptr) if traj_ptr else None,
                                          C.c_void_p(stream) if stream else None)
         if rc != 0:
+            raise IsmpcAError(_l().ismpc_a_last_error().decode())
+
+    def rollout_mc_device(self, batch, state_ptr, ticks, inst_ptr=None, pushes_ptr=None, n_push=0, stride=1, traj_ptr=None,
+                          summary_ptr=None, stream=None):
+        """ismpc_a_rollout_mc_device on raw device pointers: the closed loop with per-instance velocity pushes (batch x n_push
+        ismpc_a_push entries, instance-major), a trajectory row every `stride` ticks and one ismpc_a_rollout_summary per instance."""
+        opt = lambda p: C.c_void_p(p) if p else None
+        rc = _l().ismpc_a_rollout_mc_device(self._h, int(batch), opt(state_ptr), opt(inst_ptr), int(ticks), opt(pushes_ptr), int(n_push),
+                                            int(stride), opt(traj_ptr), opt(summary_ptr), opt(stream))
+        if rc != 0:
+            raise IsmpcAError(_l().ismpc_a_last_error().decode())
+
+    def rollout_mc_torch(self, state_u8, ticks, pushes=None, stride=1, want_traj=True, want_summary=True, inst_u8=None):
+        """The disturbed closed loop on torch tensors.  state_u8: CUDA uint8 [batch, 96], updated in place; pushes: None or a CUDA uint8
+        tensor [batch, n_push, 24] of PUSH_A records; inst_u8: None (the handle's parameters) or CUDA uint8 [batch, 32] INST_A records.
+        Returns (traj, summary): CUDA uint8 [ticks // stride, batch, 80] or None, and CUDA uint8 [batch, 64] (ROLLOUT_SUMMARY_A) or None."""
+        import torch
+        b = state_u8.shape[0]
+        assert state_u8.is_cuda and state_u8.dtype == torch.uint8 and state_u8.shape[1] == 96 and state_u8.is_contiguous()
+        n_push = 0
+        if pushes is not None:
+            assert pushes.is_cuda and pushes.dtype == torch.uint8 and pushes.dim() == 3 and pushes.shape[0] == b and pushes.shape[2] == 24 and pushes.is_contiguous()
+            assert pushes.device == state_u8.device
+            n_push = int(pushes.shape[1])
+        if inst_u8 is not None:
+            assert inst_u8.is_cuda and inst_u8.dtype == torch.uint8 and inst_u8.shape == (b, 32) and inst_u8.is_contiguous()
+        traj = torch.empty((ticks // stride if stride >= 1 else 0, b, 80), dtype=torch.uint8, device=state_u8.device) if want_traj else None
+        summary = torch.empty((b, 64), dtype=torch.uint8, device=state_u8.device) if want_summary else None
+        stream = torch.cuda.current_stream(state_u8.device).cuda_stream
+        self.rollout_mc_device(b, state_u8.data_ptr(), ticks, inst_u8.data_ptr() if inst_u8 is not None else None,
+                               pushes.data_ptr() if n_push else None, n_push, stride,
+                               traj.data_ptr() if want_traj else None, summary.data_ptr() if want_summary else None, stream)
+        return traj, summary
+
+    def reserve(self, max_batch):
+        """Sizes the handle's scratch for batches up to max_batch now (ismpc_a_reserve) instead of stream-ordered inside the calls."""
+        if _l().ismpc_a_reserve(self._h, int(max_batch)) != 0:
             raise IsmpcAError(_l().ismpc_a_last_error().decode())
 
     def feet_init_torch(self, g, foot_plan, batch, device="cuda:0"):
