@@ -218,7 +218,16 @@ int ismpc_a_rollout_mc_device(ismpc_a_handle* h, int batch, ismpc_a_state* state
 int ismpc_a_feet_rows(const ismpc_a_handle* h);     /* rows per instance in feet_dev, once initialised             */
 int ismpc_a_feet_init_device(ismpc_a_handle* h, const ismpc_a_gait* g, const double* foot_plan_host, int rows,
                              int batch, double* feet_dev, void* stream);
-/* one tick (as ismpc_a_tick_batch_device) followed by the foot QP of every instance */
+/* one tick (as ismpc_a_tick_batch_device) followed by the foot QP of every instance.
+ * Lateral limits: a LEFT foot (BL, FL) may move to y in [y_prev - disp_i, y_prev + disp_o], a RIGHT foot (BR, FR) to
+ * [y_prev - disp_o, y_prev + disp_i]; every foot to x <= x_prev + disp_forw (y_prev, x_prev: its place in row fc).  All three are halved
+ * on the scripts' first ("dummy") steps: trot fc = 1, walk fc = 2 and 4.  Walk re-places a foot only at fc = 2, 4, 6, 8.
+ * END OF PLAN.  With `rows` plan rows given to ismpc_a_feet_init*_device (an instance's block is rows + ISMPC_A_FEET_PAD rows, the last
+ * plan row repeated in the padding), the foot QP of a tick that ran with footstep counter fc re-places feet when 1 <= fc <= rows - 1 and
+ * does nothing for any other fc.  It reads rows fc, fc+1 and writes rows fc+1 .. fc+ISMPC_A_FEET_PAD at the most (1-based), i.e. never
+ * outside the instance's rows + ISMPC_A_FEET_PAD rows.  An instance whose tick is flagged ISMPC_A_ST_BAD_INDEX or ISMPC_A_ST_OVERFLOW,
+ * or whose base plan index is unknown, keeps its rows untouched.  The oracle (oracle/ismpc_oracle_a.c, orc_a_foot_step) follows the
+ * same rule. */
 int ismpc_a_tick_feet_batch_device(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, const double* push_dev,
                                    ismpc_a_out* out_dev, double* feet_dev, void* stream);
 int ismpc_a_rollout_feet_device(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, int ticks,

@@ -78,8 +78,8 @@ typedef struct orc_a_sim {
     orc_a_state st;
     orc_qp_fn qp;
     /* swing-foot re-placement (second quadprog of the scripts): optional, enabled by orc_a_enable_feet */
-    double* fp;                    /* foot_plan, (fprows+2) x 8, 1-based rows, columns BL(1,2) BR(3,4) FR(5,6) FL(7,8) */
-    int fprows, gait, counter;     /* `counter` of quad_walk_no_plots.m:114 (incremented with fsCounter, never wrapped) */
+    double* fp;                    /* foot_plan, (fprows+12) x 8, 1-based rows, columns BL(1,2) BR(3,4) FR(5,6) FL(7,8) */
+    int fprows, gait;              /* `counter` of quad_walk_no_plots.m:114,527 starts at 1 and moves with fsCounter: it IS fsCounter */
     double phi, disp_i, disp_o, disp_forw_feet;
 } orc_a_sim;
 
@@ -397,10 +397,13 @@ void orc_a_enable_feet(orc_a_sim* s, const orc_a_gait* g, const double* foot_pla
     memcpy(s->fp + 8, foot_plan, sizeof(double) * (size_t)rows * 8);
     for (int r = rows + 1; r < rows + 12; ++r) memcpy(s->fp + (size_t)r * 8, foot_plan + (size_t)(rows - 1) * 8, 64);   /* MATLAB would auto-grow; never read */
     s->gait = g->gait; s->phi = g->phi; s->disp_i = g->disp_i; s->disp_o = g->disp_o; s->disp_forw_feet = g->disp_forw;
-    s->counter = 1;
 }
 int orc_a_foot_rows(const orc_a_sim* s) { return s->fprows; }
 void orc_a_get_foot_plan(const orc_a_sim* s, double* dst) { memcpy(dst, s->fp + 8, sizeof(double) * (size_t)s->fprows * 8); }
+/* the plan with the ORC_A_FEET_PAD rows behind it that the foot step may write (the product's feet_dev layout): (fprows + 8) x 8 */
+#define ORC_A_FEET_PAD 8
+void orc_a_get_foot_plan_padded(const orc_a_sim* s, double* dst) { memcpy(dst, s->fp + 8, sizeof(double) * (size_t)(s->fprows + ORC_A_FEET_PAD) * 8); }
+void orc_a_set_foot_plan_padded(orc_a_sim* s, const double* src) { memcpy(s->fp + 8, src, sizeof(double) * (size_t)(s->fprows + ORC_A_FEET_PAD) * 8); }
 
 #define FPL(r, c) s->fp[(size_t)(r) * 8 + ((c) - 1)]
 /* line through the two fixed feet, the line of opposite slope through the predicted footstep centre ("zmp"),
@@ -437,22 +440,25 @@ static void foot_tick_trot(orc_a_sim* s, int fc, double zx, double zy)
     }
     /* quadprog(eye(4), -target, A, b): separable, so the minimiser is the projection on the box */
     const double lim_o = (fc == 1) ? dobd / 2 : dobd, lim_i = (fc == 1) ? di / 2 : di, lim_f = (fc == 1) ? df / 2 : df;
-    /* first foot of the pair: y in [y_prev - disp_i, y_prev + disp_o], x <= x_prev + disp_forw ; second: y in [y_prev - disp_o, y_prev + disp_i] */
+    /* left feet (BL, FL): y in [y_prev - disp_i, y_prev + disp_o]; right feet (BR, FR): y in [y_prev - disp_o, y_prev + disp_i]; both
+     * x <= x_prev + disp_forw (quad_as_bip_no_plots.m:377-382, 402-407).  The pair is held by column: its first foot is BL (left) on odd
+     * steps and BR (right) on even ones. */
+    const double dn1 = odd ? lim_i : lim_o, up1 = odd ? lim_o : lim_i;
     {
         const double px = FPL(fc, m1), py = FPL(fc, m1 + 1);
-        FPL(fc + 1, m1 + 1) = clipd(FPL(fc + 1, m1 + 1), py - lim_i, py + lim_o);
+        FPL(fc + 1, m1 + 1) = clipd(FPL(fc + 1, m1 + 1), py - dn1, py + up1);
         if (FPL(fc + 1, m1) > px + lim_f) FPL(fc + 1, m1) = px + lim_f;
     }
     {
         const double px = FPL(fc, m2), py = FPL(fc, m2 + 1);
-        FPL(fc + 1, m2 + 1) = clipd(FPL(fc + 1, m2 + 1), py - lim_o, py + lim_i);
+        FPL(fc + 1, m2 + 1) = clipd(FPL(fc + 1, m2 + 1), py - up1, py + dn1);
         if (FPL(fc + 1, m2) > px + lim_f) FPL(fc + 1, m2) = px + lim_f;
     }
 }
 
 static void foot_tick_walk(orc_a_sim* s, int fc, double zx, double zy)
 {
-    const int counter = s->counter;
+    const int counter = fc;                             /* quad_walk_no_plots.m:114,527: starts at 1, incremented with fsCounter */
     if (!(counter == 2 || counter == 4 || counter == 6 || counter == 8)) return;
     const double di = s->disp_i, dobd = s->disp_o, df = s->disp_forw_feet;
     /* moving foot column, the two "fixed" feet whose diagonal is used (first two pairs of the `fixed` argument) */
@@ -480,6 +486,17 @@ static void foot_tick_walk(orc_a_sim* s, int fc, double zx, double zy)
     }
 }
 #undef FPL
+
+/* The second quadprog of one tick, alone: fc = the fsCounter the tick ran with, (zx, zy) = its first predicted footstep.
+ * END OF PLAN (the rule of include/ismpc_a.h): feet are re-placed for 1 <= fc <= fprows - 1, so the rows written, fc+1 .. fc+8, stay
+ * inside the plan's fprows + ORC_A_FEET_PAD rows.  Returns 1 when the step ran. */
+int orc_a_foot_step(orc_a_sim* s, int fc, double zx, double zy)
+{
+    if (!s->fp || fc < 1 || fc > s->fprows - 1) return 0;
+    if (s->gait == 0) foot_tick_trot(s, fc, zx, zy);
+    else foot_tick_walk(s, fc, zx, zy);
+    return 1;
+}
 
 /* foot_*.txt rows (quad_as_bip_no_plots.m:482-509 / quad_walk_no_plots.m:562-613): dst = 4 x nrows x 3, order fl, fr, rl, rr */
 int orc_a_foot_trajectories(const orc_a_sim* s, int sim_duration, double* dst)
@@ -582,14 +599,10 @@ int orc_a_tick(orc_a_sim* s, double push_x, double push_y, orc_a_tick_out* out, 
     out->vel_after[0] = s->st.xd; out->vel_after[1] = s->st.yd;       /* xd_store(j), yd_store(j) */
 
     /* second quadprog: swing feet of the NEXT footstep row (uses this tick's predicted footstep and the old fsCounter) */
-    if (s->fp && fc + 9 <= s->fprows + 10) {
-        if (s->gait == 0) foot_tick_trot(s, fc, s->st.pred_x, s->st.pred_y);
-        else foot_tick_walk(s, fc, s->st.pred_x, s->st.pred_y);
-    }
+    (void)orc_a_foot_step(s, fc, s->st.pred_x, s->st.pred_y);
     /* footstep bookkeeping, :522-556 */
     if (j + 1 >= fs_timing(s, fc + 1)) {
         const int nfc = fc + 1;
-        s->counter += 1;                                                 /* quad_walk_no_plots.m:527 */
         s->st.fc = nfc;
         s->st.cur_x = s->st.pred_x; s->st.cur_y = s->st.pred_y;
         const double dx = s->st.pred_x - s->fsx[nfc], dy = s->st.pred_y - s->fsy[nfc];

@@ -70,6 +70,9 @@ def _lib():
         lib.orc_a_enable_feet.argtypes = [C.c_void_p, C.POINTER(Gait), C.c_void_p, C.c_int]
         lib.orc_a_foot_rows.argtypes = [C.c_void_p]
         lib.orc_a_get_foot_plan.argtypes = [C.c_void_p, C.c_void_p]
+        lib.orc_a_get_foot_plan_padded.argtypes = [C.c_void_p, C.c_void_p]
+        lib.orc_a_set_foot_plan_padded.argtypes = [C.c_void_p, C.c_void_p]
+        lib.orc_a_foot_step.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
         lib.orc_a_foot_trajectories.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         lib.orc_a_load_shifted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int]
         lib._a_ready = True
@@ -114,12 +117,32 @@ class SimA:
                           sx.ctypes.data_as(C.c_void_p), sy.ctypes.data_as(C.c_void_p))
         return (out[0], sx, sy) if want_solution else out[0]
 
-    def enable_feet(self):
-        """Turn on the swing-foot re-placement QPs (second quadprog of the scripts) for this run."""
-        fp = np.zeros((self.g.n_gait + 2, 8)); ce = np.zeros((self.g.n_gait + 1, 2))
-        used = _lib().orc_a_plan(C.byref(self.g), fp.ctypes.data_as(C.c_void_p), ce.ctypes.data_as(C.c_void_p))
-        self._fp0 = np.ascontiguousarray(fp[1:used + 1])
-        _lib().orc_a_enable_feet(self._h, C.byref(self.g), self._fp0.ctypes.data_as(C.c_void_p), used)
+    def enable_feet(self, foot_plan=None, gait=None):
+        """Turn on the swing-foot re-placement QPs (second quadprog of the scripts) for this run; foot_plan: the generator's own
+        (default) or a caller's [rows, 8], e.g. a truncated one; gait: the record whose heading and limits the QPs use (default: the
+        run's own)."""
+        if foot_plan is None:
+            fp = np.zeros((self.g.n_gait + 2, 8)); ce = np.zeros((self.g.n_gait + 1, 2))
+            used = _lib().orc_a_plan(C.byref(self.g), fp.ctypes.data_as(C.c_void_p), ce.ctypes.data_as(C.c_void_p))
+            foot_plan = fp[1:used + 1]
+        self._fp0 = np.ascontiguousarray(foot_plan, dtype=np.float64)
+        _lib().orc_a_enable_feet(self._h, C.byref(gait if gait is not None else self.g), self._fp0.ctypes.data_as(C.c_void_p), self._fp0.shape[0])
+
+    FEET_PAD = 8
+
+    def foot_plan_padded(self):
+        """The plan with the FEET_PAD rows behind it that the foot step may write: the product's per-instance layout."""
+        fp = np.zeros((_lib().orc_a_foot_rows(self._h) + self.FEET_PAD, 8)); _lib().orc_a_get_foot_plan_padded(self._h, fp.ctypes.data_as(C.c_void_p))
+        return fp
+
+    def set_foot_plan_padded(self, fp):
+        fp = np.ascontiguousarray(fp, dtype=np.float64)
+        assert fp.shape == (_lib().orc_a_foot_rows(self._h) + self.FEET_PAD, 8)
+        _lib().orc_a_set_foot_plan_padded(self._h, fp.ctypes.data_as(C.c_void_p))
+
+    def foot_step(self, fc, z):
+        """The second quadprog alone: the tick ran with footstep counter fc and predicted z = (f0x, f0y).  True when it re-placed."""
+        return bool(_lib().orc_a_foot_step(self._h, int(fc), float(z[0]), float(z[1])))
 
     def foot_plan(self):
         n = _lib().orc_a_foot_rows(self._h)

@@ -33,7 +33,7 @@ __global__ void ismpc_a_feet_kernel(const FeetParamsSet fset, const ismpc_a_inst
     if (pl < 0 || pl >= nplans) return;
     const FeetParams fpz = fset.p[pl];
     const int fc = prev[b].fc;                                   // the fsCounter this tick ran with
-    if (fc < 1 || fc + 8 >= fpz.rows) return;
+    if (fc < 1 || fc + 8 >= fpz.rows) return;                    // end-of-plan rule of ismpc_a.h: rows fc+1 .. fc+8 stay inside the instance's block
     double* fp = feet + (size_t)b * fpz.rows * 8;
 #define FPL(r, c) fp[(size_t)((r) - 1) * 8 + ((c) - 1)]
     const double zx = out[b].f0[0], zy = out[b].f0[1];           // predicted_xfs(1), predicted_yfs(1)
@@ -57,11 +57,14 @@ __global__ void ismpc_a_feet_kernel(const FeetParamsSet fset, const ismpc_a_inst
             FPL(fc + 1, f1) = FPL(fc, f1); FPL(fc + 1, f1 + 1) = FPL(fc, f1 + 1); FPL(fc + 1, f2) = FPL(fc, f2); FPL(fc + 1, f2 + 1) = FPL(fc, f2 + 1);
         }
         const double lo_ = (fc == 1) ? dob / 2 : dob, li_ = (fc == 1) ? di / 2 : di, lf_ = (fc == 1) ? df / 2 : df;
+        // left feet (BL, FL) have their outer side up, right feet (BR, FR) down (quad_as_bip_no_plots.m:393-407): the pair is held by
+        // column here, so the first foot is the left one on odd steps (BL) and the right one on even steps (BR)
+        const double dn1 = odd ? li_ : lo_, up1 = odd ? lo_ : li_;
         { const double px = FPL(fc, m1), py = FPL(fc, m1 + 1);
-          FPL(fc + 1, m1 + 1) = clipd(FPL(fc + 1, m1 + 1), py - li_, py + lo_);
+          FPL(fc + 1, m1 + 1) = clipd(FPL(fc + 1, m1 + 1), py - dn1, py + up1);
           if (FPL(fc + 1, m1) > px + lf_) FPL(fc + 1, m1) = px + lf_; }
         { const double px = FPL(fc, m2), py = FPL(fc, m2 + 1);
-          FPL(fc + 1, m2 + 1) = clipd(FPL(fc + 1, m2 + 1), py - lo_, py + li_);
+          FPL(fc + 1, m2 + 1) = clipd(FPL(fc + 1, m2 + 1), py - up1, py + dn1);
           if (FPL(fc + 1, m2) > px + lf_) FPL(fc + 1, m2) = px + lf_; }
     } else {
         const int counter = fc;                                  // `counter` (quad_walk_no_plots.m:114,527) starts at 1 and moves with fsCounter

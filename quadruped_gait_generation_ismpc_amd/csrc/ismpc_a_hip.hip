@@ -725,7 +725,7 @@ int ismpc_a_feet_init_device(ismpc_a_handle* h, const ismpc_a_gait* g, const dou
     if (int rc = feet_upload(h, g, foot_plan_host, rows, 1, &h->feet)) return rc;
     const int rp = h->feet.rows;
     if (batch > 0) {
-        hipLaunchKernelGGL(ismpc_a_feet_fill, dim3(std::min(1024, (batch * rp * 8 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+        hipLaunchKernelGGL(ismpc_a_feet_fill, dim3(std::min(1024, (int)(((size_t)batch * rp * 8 + 255) / 256))), dim3(256), 0, static_cast<hipStream_t>(stream),
                            (const double*)h->feet_base, feet_dev, rp, batch);
         HIP_TRY_A(hipGetLastError());
     }

@@ -285,6 +285,20 @@ class GaitGenerator:
             raise IsmpcAError(_l().ismpc_a_last_error().decode())
         return traj
 
+    def tick_feet_torch(self, state_u8, feet, push=None):
+        """One tick with the handle's parameters followed by the swing-foot QP of every instance (ismpc_a_tick_feet_batch_device).
+        feet: the caller's float64 [batch, rows + FEET_PAD, 8] block, updated in place; push: None or CUDA float64 [batch, 2]."""
+        import torch
+        b = state_u8.shape[0]
+        out = torch.empty((b, 80), dtype=torch.uint8, device=state_u8.device)
+        stream = torch.cuda.current_stream(state_u8.device).cuda_stream
+        rc = _l().ismpc_a_tick_feet_batch_device(self._h, b, C.c_void_p(state_u8.data_ptr()),
+                                                 C.c_void_p(push.data_ptr()) if push is not None else None, C.c_void_p(out.data_ptr()),
+                                                 C.c_void_p(feet.data_ptr()), C.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise IsmpcAError(_l().ismpc_a_last_error().decode())
+        return out
+
     def tick_feet_inst_torch(self, state_u8, inst_u8, feet, push=None):
         import torch
         b = state_u8.shape[0]

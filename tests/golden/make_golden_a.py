@@ -80,5 +80,22 @@ def make_prerolls():
         print("preroll", name, "x_end", tab["x"][-1], tab["y"][-1])
 
 
+def make_feet_states():
+    """States of the swing-foot tests (tests/helpers/feet_cases.py): the oracle's unpushed closed loop at two ticks per footstep
+    counter 1 .. 10, in the product's ismpc_a_state layout, with the oracle's first predicted footstep of the tick from each."""
+    import importlib.util
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    spec = importlib.util.spec_from_file_location("feet_cases", os.path.join(os.path.dirname(HERE), "helpers", "feet_cases.py"))
+    F = importlib.util.module_from_spec(spec); spec.loader.exec_module(F)
+    arrs = {}
+    for name, (kind, phi) in F.CONFIGS.items():
+        st, f0 = F.harvest_from_oracle(kind, phi)
+        arrs[name + "_state"] = st.view(np.uint8).reshape(len(st), -1); arrs[name + "_f0"] = f0
+        print("feet states", name, len(st))
+    np.savez_compressed(os.path.join(HERE, "feetA_states.npz"), **arrs)
+
+
 if __name__ == "__main__":
     make_prerolls()
+    make_feet_states()
