@@ -66,7 +66,14 @@ extern "C" {
 /* the bits that say a tick's result is not a solution of the three QPs */
 #define ISMPC_ST_ERROR_MASK (ISMPC_ST_X_INFEASIBLE | ISMPC_ST_Y_INFEASIBLE | ISMPC_ST_BAD_INDEX | ISMPC_ST_Z_FAILED)
 
-/* ---- parameters: parameters.cpp:9-45 and MPCSolver.cpp:253-255 ---------- */
+/* ---- parameters: parameters.cpp:9-45 and MPCSolver.cpp:253-255 ----------
+ * Gait timing a handle takes: S >= 0 single-support and 1 <= F <= ISMPC_F_MAX double-support samples, in any relation to the
+ * horizon (S + F above, at or below N), with S + F <= 4096.  The vertical QP pins u_i = 0 on up to min(F, N)
+ * samples per tick (MPCSolver.cpp:223-243), and the inequality fallback keeps one pinned sample per lane of a wavefront: F > 64 is
+ * refused by ismpc_create, ismpc_create_sweep and ismpc_create_plans with ISMPC_E_UNSUPPORTED, before the device is touched.
+ * Parameter sweeps, and multi-plan handles with n_sets > 1, build their tables on the device for F <= 16 (ISMPC_E_UNSUPPORTED
+ * beyond); a multi-plan handle with one set takes every F a plain handle takes.                                              */
+#define ISMPC_F_MAX 64
 typedef struct ismpc_params {
     int32_t N;                 /* horizon samples           parameters.cpp:42 (=100)       */
     int32_t S;                 /* single-support samples    parameters.cpp:43 (=35)        */

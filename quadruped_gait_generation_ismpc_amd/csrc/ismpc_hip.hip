@@ -352,9 +352,12 @@ Knobs read_knobs()
     return k;
 }
 
-// Everything that can be said about the arguments of ismpc_create_plans (P > 0) and ismpc_create_sweep, said before the device is touched
+// Everything that can be said about the arguments of ismpc_create, ismpc_create_plans (P > 0) and ismpc_create_sweep, said before the device is touched
 int check_args(const ismpc_params* params, int K, bool sweep, const double* ftsp, int rows, int P, const Knobs& knobs)
 {
+    // every handle: the inequality fallback keeps the e-th pinned sample of an equality pattern in lane e of its wavefront (z_fetch / z_project,
+    // ismpc_b_affine.hpp), and a pattern pins up to min(F, N) samples
+    if (params[0].F > ISMPC_F_MAX) return fail(ISMPC_E_UNSUPPORTED, "F > 64 double-support samples: the vertical fallback holds one pinned sample per lane of a wavefront");
     if (P) {
         if (P < 1 || P > 32767) return fail(ISMPC_E_INVALID, "a multi-plan handle holds 1 .. 32767 footstep plans");
         if (K < 1 || K > 65535) return fail(ISMPC_E_INVALID, "a multi-plan handle holds 1 .. 65535 parameter sets");

@@ -198,13 +198,16 @@ def run_step(q, O, lay, N):
     return cached(("step", lay, N), make)
 
 
-def check_against_oracle(q, N, lay, tin, out, ref):
-    """The rules of test_gpu_parity.test_against_oracle_seeded, and the fallback's iteration byte on the active instances."""
+def check_against_oracle(q, N, lay, tin, out, ref, on_boundary=None):
+    """The rules of test_gpu_parity.test_against_oracle_seeded, and the fallback's iteration byte on the active instances.
+    on_boundary(record, band): the feasibility-band rule for a case that does not run with the default parameters and plan (which
+    _on_feasibility_boundary builds); the rule and the band are the same."""
     ok = (ref["status"] & q.ST_ERROR_MASK) == 0
     assert ((out["status"] != ref["status"]) & ok).sum() == 0, (np.flatnonzero((out["status"] != ref["status"]) & ok), out["status"], ref["status"])
     diff = (out["status"] & q.ST_ERROR_MASK) != (ref["status"] & q.ST_ERROR_MASK)
     for b in np.where(diff)[0]:
-        assert _on_feasibility_boundary(q, N, tin[b], band=1e-9), (b, out["status"][b], ref["status"][b])
+        near = on_boundary(tin[b], 1e-9) if on_boundary is not None else _on_feasibility_boundary(q, N, tin[b], band=1e-9)
+        assert near, (b, out["status"][b], ref["status"][b])
     assert_parity(q, out, ref, z_fallback=(lay != "dense"))
     act = (ref["status"] & q.ST_Z_INEQ_ACTIVE) != 0
     both = act & (((ref["status"] | out["status"]) & q.ST_ERROR_MASK) == 0)
