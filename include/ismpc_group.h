@@ -85,6 +85,46 @@ int ismpc_group_order_after(ismpc_group* g, int local, void* stream);
 /* Sizes the device buffers for batches up to max_batch now (otherwise they grow, with a synchronisation, inside a call). */
 int ismpc_group_reserve(ismpc_group* g, int max_batch);
 
+/* DISTURBED closed loops through the group: ismpc_rollout_mc_device (ismpc.h: pushes, a trajectory row every traj_stride ticks,
+ * per-instance summaries) on every local device's contiguous shard, then ONE fused collective -- between one ncclGroupStart /
+ * ncclGroupEnd, one in-place all-gather per requested output -- so that every device ends with the summaries and the trajectories
+ * of all `batch` instances.  One exchange per ROLLOUT, not per tick.  All buffers are the caller's, per local device l:
+ *   state_dev[l]        the SHARD's count_l states, advanced in place; they stay with their owner (no exchange)
+ *   pushes_dev[l]       the shard's count_l x n_push entries (the list is NULL with n_push = 0; entries of empty shards are not read)
+ *   summary_all_dev[l]  `batch` records; the device's rollout writes its shard straight to summary_all_dev[l] + first
+ *   traj_all_dev[l]     batch x rows records, rows = ticks / traj_stride, INSTANCE-major (row r of instance i at [i * rows + r]), so
+ *                       that a shard is the one block starting at first * rows: the device's rollout writes tick-major into a
+ *                       buffer the group owns, ismpc_records_to_instance_major_device's kernel moves that to its block
+ * Either output list may be NULL (with both NULL no collective is enqueued); ticks < traj_stride gives zero rows and touches no
+ * trajectory byte; ticks = 0 gives the empty summary of ismpc.h on every rank; a rank with an empty shard launches nothing and
+ * takes part in the collective.  Ragged shards take the per-root broadcasts of the tick path.
+ * Asynchronous: ismpc_group_sync drains it; ismpc_group_rollout_wait_on makes a caller stream wait for the MOST RECENT rollout of
+ * local device `local` -- its collective, and with it the device's own kernels, so the advanced states too -- and does nothing
+ * before the first rollout.  The outputs may be reused by the next call: before a device's kernels of rollout k + 1 write, the
+ * collective of rollout k has completed on that device (stream-side wait).  ismpc_group_order_after orders the launch stream
+ * behind the caller's producers, as for a step.  The double buffers of ismpc_group_step_device are not touched: a step between two
+ * rollouts leaves all three results intact.  ismpc_group_reserve_rollout sizes the group's tick-major buffer (max_rows rows of the
+ * largest shard of max_batch) and the handles' scratch now; otherwise the buffer grows inside a call, after draining that device's
+ * launch and side streams.
+ * Every shard -- final states, summaries, trajectory -- is byte-identical to ismpc_rollout_mc_device of the same count_l records on
+ * a plain handle built the same way (a per-shard call: another batch size may select another lane layout).
+ * ISMPC_E_INVALID before the device is touched, ismpc_group_last_error naming the argument: a null group; what ismpc_rollout_mc_device
+ * refuses (negative batch, ticks, first_frame or n_push, traj_stride < 1, n_push > 0 with a null list, batch > 0 with a null state
+ * list); a null state or push entry of a non-empty shard; a null entry in a non-null traj_all_dev or summary_all_dev; a trajectory
+ * pointer that is not 16-byte aligned.  batch = 0 returns ISMPC_OK.                                                      */
+int ismpc_group_rollout_mc_device(ismpc_group* g, int batch, ismpc_tick_in* const* state_dev, int first_frame, int ticks,
+                                  const ismpc_push* const* pushes_dev, int n_push, int traj_stride,
+                                  ismpc_tick_out* const* traj_all_dev, ismpc_rollout_summary* const* summary_all_dev);
+int ismpc_group_rollout_wait_on(ismpc_group* g, int local, void* stream);
+int ismpc_group_reserve_rollout(ismpc_group* g, int max_batch, int max_rows);
+
+/* The kernel behind the trajectory: count instances x rows records of 80 bytes (ismpc_tick_out, ismpc_a_out), tick-major
+ * [row][instance] -> instance-major, dst_block[i * rows + row] = tick_major[row * count + i]; dst_block is where instance 0 of the
+ * source goes (a shard's block of a larger buffer: all_dev + first * rows).  Enqueued on `stream` (a hipStream_t) of the current
+ * device; the buffers must not overlap.  rows = 0 or count = 0 enqueues nothing.  ISMPC_E_INVALID before the device is touched:
+ * negative rows or count, a null pointer with a non-empty shape, a pointer that is not 16-byte aligned.                    */
+int ismpc_records_to_instance_major_device(const void* tick_major, int rows, int count, void* dst_block, void* stream);
+
 /* ---- Formulation A (the MATLAB generators' tick, include/ismpc_a.h) --------------------------------------------- */
 int ismpc_a_group_create(const ismpc_a_params* p, const double* center, const int* devices, int n, ismpc_a_group** out);
 int ismpc_a_group_create_rank(const ismpc_a_params* p, const double* center, int device,
@@ -110,6 +150,16 @@ int ismpc_a_group_wait_on(ismpc_a_group* g, int local, int buf, void* stream);
 int ismpc_a_group_sync(ismpc_a_group* g);
 int ismpc_a_group_order_after(ismpc_a_group* g, int local, void* stream);
 int ismpc_a_group_reserve(ismpc_a_group* g, int max_batch);
+/* ismpc_a_rollout_mc_device (ismpc_a.h) through the group: as ismpc_group_rollout_mc_device, same layout, ordering, reuse rule and
+ * errors.  inst_dev is NULL (the handles' parameters) or lists the shards' per-instance records (a NULL entry: that shard runs on
+ * the handle's parameters); the summaries are 64-byte ismpc_a_rollout_summary records, and ticks = 0 gives the empty summary of
+ * ismpc_a.h.  Either precision (ismpc_a_group_set_precision).  Every shard is byte-identical to ismpc_a_rollout_mc_device of the
+ * same count_l records on a plain handle built the same way (plans added, precision set).                                */
+int ismpc_a_group_rollout_mc_device(ismpc_a_group* g, int batch, ismpc_a_state* const* state_dev, const ismpc_a_inst* const* inst_dev,
+                                    int ticks, const ismpc_a_push* const* pushes_dev, int n_push, int traj_stride,
+                                    ismpc_a_out* const* traj_all_dev, ismpc_a_rollout_summary* const* summary_all_dev);
+int ismpc_a_group_rollout_wait_on(ismpc_a_group* g, int local, void* stream);
+int ismpc_a_group_reserve_rollout(ismpc_a_group* g, int max_batch, int max_rows);
 
 const char* ismpc_group_last_error(void);     /* thread-local, never NULL: errors of the entry points of this header */
 /* RCCL version the process bound (ncclGetVersion), 0 when RCCL could not be loaded.                                  */
