@@ -180,7 +180,7 @@ template <int R, int LPI> constexpr int wave_lds_double2_fb() { return wave_lds_
 // without the midpoint cut 1.583-1.650 | 43.3-44.2, without the clamp cut 1.577-1.631 | 42.6-43.0, without the gate's 1.593-1.631 | 43.1-43.6.
 // Dropped: dt_n of a slot from a per-layout table instead of the select (a new table, upload and DevConst field; -26 selects, +13 loads per
 // lane): the whole set above is WITH it, this build without -- a tie on both figures, so the select stays.
-template <int R, int LPI, int SW = 0, bool MF = true>
+template <int R, int LPI, int SW = 0, bool MF = true, bool MASKS = MF>
 __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lane, const QState& s, QOut& o, double* __restrict__ u_traj_inst,
                                                 double2* __restrict__ lds_wave, const bool keep)
 {
@@ -375,7 +375,6 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
     // is observable in the two-launch form and with ISMPC_Z_FALLBACK=0.)  A group that is not live keeps tau at its start; its
     // ux0 / uy0 are then not the converged ones, and none of it is stored (every store of a tail group is guarded by `valid`).
     const bool stage3 = run && Grp<LPI>::bcast0(lam0_l) > c.gate;
-    bool live[2] = {MF ? keep && stage3 : true, MF ? keep && stage3 : true};
     int st3 = 0;
     if (!(q0 > 0.0)) {                                                       // no sample can move the ZMP
 #pragma unroll
@@ -384,6 +383,70 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
             if (Tq[ax] > 1e-300) st3 |= (ax == 0 ? ISMPC_ST_X_INFEASIBLE : ISMPC_ST_Y_INFEASIBLE);
         }
     }
+    // MASKS (the per-tick kernels, tied to MF as LEAN is): which groups are live is kept in two wave-wide 64-bit lane masks, one per axis, in
+    // scalar registers.  As per-lane bools the two flags sat packed in one VGPR and every "is anyone live" test was a round trip mask -> VGPR ->
+    // mask (v_and_b32_sdwa, v_cmp_eq_u32, v_cndmask 0/1, v_cmp_ne_u32), the update below a three-deep exec nest with copies of tau.  Here the
+    // tests are s_cmp on the mask, a mask is only ever written from a ballot at a point every lane reaches (never inside divergent code), and a
+    // lane reads its flag back with the inverse ballot of that wave-uniform value.
+    // Every QP sees the iterate sequence it saw: a lane's bit of lv[ax] is the live[ax] it had at the same point of the same pass.
+    //   - cnt == prev clears the bit exactly where `live && cnt == prev` cleared the flag (and-not of a ballot taken in all lanes).
+    //   - rem, tn and the three compares are computed in every lane from the group's sums; only a live lane stores anything of them.  A live lane
+    //     stores ++its; with allsat = !(qfree > 0) (true for qfree = 0 and for NaN) tau = INFINITY and the infeasible bit under the same test
+    //     as before, and the bit goes; otherwise tn = rem * frcp(qfree) and grow = tn > tau (false for a NaN tn): tau = tn and prev = cnt if it
+    //     grows, nothing but the cleared bit if not.  Those are the three branches the loop had, as selects.  q0 <= 0 is settled before the loop
+    //     as it was: such a group enters live with tau = INFINITY or 0, counts, and leaves through cnt == prev or through allsat exactly as before.
+    //   - A lane that is not live computes garbage (frcp of 0 included: rcp and fma raise nothing on this path) and stores none of it; every
+    //     outcome mask is and-ed with the live mask.
+    //   - One ballot per compare, combined with s_and / s_andn2: a ballot of `a && b` comes back through v_cndmask 0/1 + v_cmp_ne.
+    // Measured (the record is DESIGN section 5), parent's library against this one, alternated: SQ_INSTS_VALU / SQ_WAVES of the headline
+    // 1 714.97 -> 1 654.13, 65 536 instances 1.606-1.628 -> 1.668-1.709 10^9 ticks/s (every run above every run of the parent), isolated launch
+    // 39.7-42.7 -> 37.9-40.8 us.  The sum pass under the exec mask, tried on top, was slower (46.1-47.6 us) and is not here.
+    // The rollout (MF = false) keeps the loop it had, verbatim: with the masks one of its instantiations does not compile (the backend's verifier
+    // on the null test of the LDS window, as in the disturbed rollout) and several of those that do gain spilled vector registers.
+    if constexpr (MASKS) {
+        const unsigned long long lv0 = __builtin_amdgcn_ballot_w64(MF ? keep && stage3 : true);
+        unsigned long long lv[2] = {lv0, lv0};
+        for (int it = 0; it < N + 2; ++it) {
+            if ((lv[0] | lv[1]) == 0ull) break;
+#pragma unroll
+            for (int ax = 0; ax < 2; ++ax) {
+                if (lv[ax] == 0ull) continue;                                 // this axis is done in every group of the wavefront (the other one
+                                                                              // may keep the loop alive: scripts/knapsack_model.py)
+                int cl = 0;
+#pragma unroll
+                for (int r = 0; r < R; ++r) cl += (tau[ax] * fabs(a[r]) >= h) ? 1 : 0;
+                const int cnt = Grp<LPI>::sum_i(cl);
+                lv[ax] &= ~__builtin_amdgcn_ballot_w64(cnt == prev[ax]);      // active set unchanged: exact
+                if (lv[ax] == 0ull) continue;
+                double ssat = 0.0, qfree = 0.0;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    // 0 / 1 masks and two fused multiply-adds instead of two 64-bit selects and two adds: the same sums bit for bit
+                    // (fma(1, x, s) = s + x rounded once, fma(0, x, s) = s), a third fewer instructions in the loop the kernel spends most in
+                    const double ab = fabs(a[r]);
+                    const bool sat = tau[ax] * ab >= h;
+                    const double ms = sat ? 1.0 : 0.0, mf = sat ? 0.0 : 1.0;
+                    ssat = fma(ms, ab, ssat); qfree = fma(mf, a[r] * a[r], qfree);
+                }
+                ssat = Grp<LPI>::sum(ssat); qfree = Grp<LPI>::sum(qfree);
+                const double rem = fma(-h, ssat, Tq[ax]);
+                const double tn = rem * frcp(qfree);
+                // the outcomes as lane masks of the live lanes (one ballot per compare, combined on the scalar unit); each store is one
+                // select under the inverse ballot of its mask.  allsat = !(qfree > 0): everything saturated; grow = !allsat && tn > tau
+                const unsigned long long m_live = lv[ax];
+                const unsigned long long b_free = __builtin_amdgcn_ballot_w64(qfree > 0.0);
+                const unsigned long long m_grow = m_live & b_free & __builtin_amdgcn_ballot_w64(tn > tau[ax]);
+                const unsigned long long m_sat = m_live & ~b_free;
+                const unsigned long long m_inf = m_sat & __builtin_amdgcn_ballot_w64(rem > fma(h * ssat, 1e-12, 1e-300));
+                its[ax] += __builtin_amdgcn_inverse_ballot_w64(m_live) ? 1 : 0;
+                st3 |= __builtin_amdgcn_inverse_ballot_w64(m_inf) ? (ax == 0 ? ISMPC_ST_X_INFEASIBLE : ISMPC_ST_Y_INFEASIBLE) : 0;
+                tau[ax] = __builtin_amdgcn_inverse_ballot_w64(m_sat) ? INFINITY : __builtin_amdgcn_inverse_ballot_w64(m_grow) ? tn : tau[ax];
+                prev[ax] = __builtin_amdgcn_inverse_ballot_w64(m_grow) ? cnt : prev[ax];
+                lv[ax] = m_grow;
+            }
+        }
+    } else {
+    bool live[2] = {true, true};
     for (int it = 0; it < N + 2; ++it) {
         if (__builtin_amdgcn_ballot_w64(live[0] || live[1]) == 0ull) break;
 #pragma unroll
@@ -420,6 +483,7 @@ __device__ __forceinline__ bool tick_group_core(const DevConst& c, const int lan
                 }
             }
         }
+    }
     }
 
     STAMP(4);                                         // knapsack Newton done
