@@ -155,7 +155,7 @@ int ismpc_a_rollout_inst_device(ismpc_a_handle* h, int batch, ismpc_a_state* sta
  * parameters) or ismpc_a_rollout_inst_device (batch records) -- same working-set history, same behaviour on error ticks: the loop goes
  * on -- with the three additions of ismpc_rollout_mc_device (ismpc.h).  Works on every handle those two take, in either precision.  One
  * prologue launch and the solver launch(es) per tick, as there, and one small launch behind the last tick when a summary is asked for.
- * No swing-foot variant: the call has no feet_dev argument.
+ * The swing-foot variant, with a feet_dev argument, is ismpc_a_rollout_mc_feet_device further down.
  *
  * PUSHES.  The scripts' impulsive velocity "bang" (quad_walk_no_plots.m:134-148) as a table: pushes_dev holds n_push entries per
  * instance, instance-major (entry k of instance i at [i * n_push + k]).  An entry applies at tick t when its tick == t and no earlier
@@ -245,9 +245,68 @@ int ismpc_a_tick_feet_batch_inst_device(ismpc_a_handle* h, int batch, ismpc_a_st
                                         const double* push_dev, ismpc_a_out* out_dev, double* feet_dev, void* stream);
 int ismpc_a_rollout_feet_inst_device(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, const ismpc_a_inst* inst_dev,
                                      int ticks, ismpc_a_out* out_traj_dev, double* feet_dev, void* stream);
+/* DISTURBED closed loop WITH the swing-foot QPs: ismpc_a_rollout_mc_device (push rule, stride, summary, error behaviour: all as stated
+ * there) with ismpc_a_feet_kernel behind the solver launch(es) of every tick, exactly as ismpc_a_tick_feet_batch[_inst]_device launches
+ * it -- behind the fp64 re-solve launch of an fp32 handle too.  Works on every handle and launch form ismpc_a_rollout_feet[_inst]_device
+ * takes.  feet_dev is batch x ismpc_a_feet_rows(h) x 8, updated in place.
+ *   FEET DO NOT FEED BACK.  For the same arguments state_dev, traj_dev and summary_dev are byte-identical to ismpc_a_rollout_mc_device's.
+ *   NO DISTURBANCE.  With n_push = 0, traj_stride = 1 and both summaries NULL, state, trajectory and feet_dev are byte-identical to
+ *     ismpc_a_rollout_feet_device / ismpc_a_rollout_feet_inst_device.
+ *   WITH PUSHES everything, feet_dev included, is byte-identical to the caller-driven loop: ismpc_a_set_warm_history(h, 1) on a fresh
+ *     handle, then `ticks` calls of ismpc_a_tick_feet_batch[_inst]_device, each given a batch x 2 push array.
+ *   OUTPUT RECORDS.  The foot QP reads the tick's f0 and status, so every tick writes an output record: into its trajectory row when it
+ *     has one, else into the handle's scratch records (the ones ismpc_a_rollout_mc_device uses for ticks only the summary wants;
+ *     ismpc_a_reserve sizes them).
+ *   FEET SUMMARY.  feet_summary_dev is NULL or batch records, written by one launch behind the last tick: every instance's block of
+ *     feet_dev, all ismpc_a_feet_rows(h) rows (padding included), against the handle's device copy of the base plans -- plan 0 for a plain
+ *     handle, inst[b].plan for a per-instance one, plan 0 when that index is unknown (what ismpc_a_feet_init_inst_device gave the
+ *     instance).  It describes the block AS IT STANDS: everything since ismpc_a_feet_init*_device, not only this call.  All five
+ *     reductions are independent of the order (count, min, max, fmax), so the record equals a host reduction (np.fmax) of the read-back
+ *     block to the bit; a NaN entry is ignored by max_abs_shift and counted by nonfinite and moved_rows.
+ * Returns -1 before the device is touched, ismpc_a_last_error naming the function and the argument: negative batch or ticks,
+ * traj_stride < 1, n_push < 0, n_push > 0 with a null table, batch > 0 with a null state or a null feet_dev, null handle.  Then, on the
+ * handle's device, the messages of ismpc_a_tick_feet_batch[_inst]_device: feet not initialised, a per-instance batch without
+ * ismpc_a_feet_init_inst_device.  batch = 0 returns 0; ticks = 0 runs no tick, writes the empty rollout summary and the feet summary of
+ * the block as it stands. */
+typedef struct ismpc_a_feet_summary {    /* 32 bytes */
+    int32_t moved_rows;                  /* rows of the instance's block with any of the 8 entries !(feet == base) */
+    int32_t first_moved_row;             /* 1-based; 0: none */
+    int32_t last_moved_row;              /* 1-based; 0: none */
+    int32_t nonfinite;                   /* entries of the block that are not finite */
+    double  max_abs_shift[2];            /* fmax over rows and the four x columns (0,2,4,6) / y columns (1,3,5,7) of |feet - base|, from 0.0 */
+} ismpc_a_feet_summary;
+
+int ismpc_a_rollout_mc_feet_device(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev,
+                                   const ismpc_a_inst* inst_dev,            /* NULL: the handle's parameters; else batch records */
+                                   int ticks,
+                                   const ismpc_a_push* pushes_dev, int n_push,
+                                   int traj_stride, ismpc_a_out* traj_dev,
+                                   ismpc_a_rollout_summary* summary_dev,
+                                   double* feet_dev,                        /* batch x ismpc_a_feet_rows(h) x 8, in place */
+                                   ismpc_a_feet_summary* feet_summary_dev,  /* NULL, or batch records */
+                                   void* stream);
+
 /* Host: the four foot files of one instance.  foot_plan: rows x 8 (as left by the rollout); dst: 4 x n x 3 in the
  * order fl, fr, rl, rr with n = (sim_duration / step) * step rows; returns n. */
 int ismpc_a_foot_trajectories(const ismpc_a_gait* g, int step, const double* foot_plan, int rows, int sim_duration, double* dst);
+/* Device: the same for a whole batch, bit for bit.  Instance b gets exactly what ismpc_a_foot_trajectories returns for the gait of its
+ * base plan (the foot rules given to ismpc_a_feet_init*_device), its own step (inst_dev = NULL: the handle's step and plan 0; else
+ * inst[b].step and inst[b].plan), its ismpc_a_feet_rows(h) rows of feet_dev and sim_duration.  dst_dev is batch x 4 x sim_duration x 3,
+ * files in the order fl, fr, rl, rr.  With n_b = (sim_duration / step_b) * step_b, rows [0, n_b) of each of the instance's four blocks
+ * are written and rows [n_b, sim_duration) are not touched; nrows_dev (NULL, or batch) gets n_b.  Where the host function would refuse
+ * (step_b < 1, sim_duration < step_b, n_b / step_b + 1 > ismpc_a_feet_rows(h), a trot plan with step_b <= 50, an unknown plan index)
+ * the instance writes nothing and gets nrows_dev[b] = -1; the call itself still returns 0.  The arithmetic is the host function's,
+ * operation for operation, with no fused multiply-add.
+ * Returns -1 before the device is touched, ismpc_a_last_error naming the function and the argument: null handle, negative batch,
+ * sim_duration < 1, batch > 0 with a null feet_dev or dst_dev.  Then the messages of ismpc_a_tick_feet_batch[_inst]_device (feet not
+ * initialised, inst_dev without ismpc_a_feet_init_inst_device).  batch = 0 returns 0. */
+int ismpc_a_foot_trajectories_device(ismpc_a_handle* h, int batch,
+                                     const ismpc_a_inst* inst_dev,           /* NULL: the handle's step and plan 0 */
+                                     const double* feet_dev,                 /* batch x ismpc_a_feet_rows(h) x 8 */
+                                     int sim_duration,
+                                     double* dst_dev,                        /* batch x 4 x sim_duration x 3 */
+                                     int32_t* nrows_dev,                     /* NULL, or batch */
+                                     void* stream);
 /* Host: write n rows of 3 values exactly as MATLAB's fprintf(file, '%d %d %d\n', row) does (integers as %d,
  * everything else as %e).  Returns 0 or a negative error. */
 int ismpc_a_write_trajectory_txt(const char* path, const double* rows3, int n);

@@ -6,4 +6,4 @@ from .solver import (MPCSolver, State, WalkState, IsmpcError, default_params, re
                      to_device, from_device, pack_reserved, KERNEL_FAMILIES,
                      ST_X_INFEASIBLE, ST_Y_INFEASIBLE, ST_Z_INEQ_ACTIVE, ST_BAD_INDEX,
                      ST_FLIGHT, ST_TICK_SKIPPED, ST_Z_NAN, ST_Z_FAILED, ST_ERROR_MASK)
-from .formulation_a import PUSH_A, ROLLOUT_SUMMARY_A, ST_ERROR_MASK_A  # noqa: F401  (Formulation A's own: formulation_a.GaitGenerator)
+from .formulation_a import PUSH_A, ROLLOUT_SUMMARY_A, FEET_SUMMARY_A, ST_ERROR_MASK_A  # noqa: F401  (Formulation A's own: formulation_a.GaitGenerator)

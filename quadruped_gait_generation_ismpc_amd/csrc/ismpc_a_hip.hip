@@ -7,12 +7,15 @@
 //                           rows-per-lane value in ismpc_a_wave_rl2.hip, _rl3.hip, _rl4.hip (launch_wave_rl*)
 //   ismpc_a_block.hpp       ismpc_a_tick_kernel: one workgroup per QP; every other F, and ISMPC_A_KERNEL=block (A/B)
 //   ismpc_a_feet.hpp        ismpc_a_feet_kernel (swing-foot re-placement after a tick), ismpc_a_feet_fill, ismpc_a_feet_fill_inst
+//   ismpc_a_feet_files.hpp  ismpc_a_feet_summary_kernel (a batch's foot plans against the base plans), ismpc_a_foot_trajectories_kernel (the
+//                           four foot files of every instance, the host writer's bits)
 //   ismpc_wave_prims.hpp    wavefront prefix sum (shared with Formulation B)
 //   ismpc_host.hpp          device guard, early return on a HIP error, growth of scratch (shared by the three ABIs)
 //   this file               the error string; host geometry (linspace_m, centreline, ismpc_a_plan, ismpc_a_foot_trajectories, the text
 //                           writer); ismpc_a_handle and its run-time knobs; the launch path (ismpc_a_tick_prologue, ismpc_a_bucket_by_F,
 //                           tick_launch, tick_feet, rollout_a); the disturbed closed loop (ismpc_a_mc_prologue, ismpc_a_mc_fold,
-//                           ismpc_a_rollout_mc_device); the extern "C" entry points
+//                           ismpc_a_rollout_mc_device, ismpc_a_rollout_mc_feet_device); ismpc_a_foot_trajectories_device; the extern "C"
+//                           entry points
 //
 // Results are the unique minimiser: validated against the oracle's null-space Goldfarb-Idnani and the
 // reference's qpOASES (tests/).  No CPU fallback.
@@ -31,6 +34,7 @@
 #include "ismpc_host.hpp"
 #include "ismpc_a_block.hpp"
 #include "ismpc_a_feet.hpp"
+#include "ismpc_a_feet_files.hpp"
 
 namespace {
 
@@ -76,6 +80,7 @@ struct ismpc_a_handle {
     int device = 0, slots = 0;
     ismpc_a_state* prev = nullptr; int prev_cap = 0;     // copy of the state the tick reads
     FeetParams feet{}; double* feet_base = nullptr;     // swing-foot QPs (ismpc_a_feet_init_device)
+    int feet_base_plans = 0;                             // base plans feet_base holds (feet_upload): what ismpc_a_feet_summary_kernel may index
     FeetParamsSet feet_set{}; int feet_plans = 0;        // ... and per base plan (ismpc_a_feet_init_inst_device)
     bool use_wave = true; int wave_blocks = 0;           // structured wavefront-per-QP kernel (default) vs workgroup-per-QP
     int cus = 0, wave_occ[16] = {0};                     // resident workgroups per CU of the wave kernels ([F - 3][precision x per-instance])
@@ -707,9 +712,10 @@ static int feet_upload(ismpc_a_handle* h, const ismpc_a_gait* gaits, const doubl
     for (int k = 0; k < nplans; ++k)
         for (int r = 0; r < rp; ++r)
             std::memcpy(&base[((size_t)k * rp + r) * 8], plans_host + ((size_t)k * rows + std::min(r, rows - 1)) * 8, 64);
-    if (h->feet_base) { (void)hipFree(h->feet_base); h->feet_base = nullptr; }
+    if (h->feet_base) { (void)hipFree(h->feet_base); h->feet_base = nullptr; h->feet_base_plans = 0; }
     HIP_TRY_A(hipMalloc((void**)&h->feet_base, base.size() * sizeof(double)));
     HIP_TRY_A(hipMemcpy(h->feet_base, base.data(), base.size() * sizeof(double), hipMemcpyHostToDevice));
+    h->feet_base_plans = nplans;
     for (int k = 0; k < nplans; ++k) {
         FeetParams& f = dst[k];
         f.gait = gaits[k].gait; f.rows = rp; f.phi = gaits[k].phi; f.disp_i = gaits[k].disp_i; f.disp_o = gaits[k].disp_o; f.disp_forw = gaits[k].disp_forw;
@@ -752,12 +758,12 @@ int ismpc_a_feet_init_inst_device(ismpc_a_handle* h, const ismpc_a_gait* gaits, 
 }
 
 static int tick_feet(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, const ismpc_a_inst* inst_dev, const double* push_dev,
-                     ismpc_a_out* out_dev, double* feet_dev, void* stream, int history = -1)
+                     ismpc_a_out* out_dev, double* feet_dev, void* stream, int history = -1, const McTick* mc = nullptr)
 {
     if (!h || !out_dev || (batch > 0 && !feet_dev) || h->feet.rows == 0) return fail_a(-1, "feet: call ismpc_a_feet_init_device first and pass an output buffer");
     if (inst_dev && h->feet_plans == 0) return fail_a(-1, "feet: per-instance batches need ismpc_a_feet_init_inst_device");
     ON_DEVICE_A(h);                                                 // the feet launch below runs on the handle's device too
-    int rc = tick_launch(h, batch, state_dev, inst_dev, push_dev, out_dev, stream, history);
+    int rc = tick_launch(h, batch, state_dev, inst_dev, push_dev, out_dev, stream, history, mc);
     if (rc || batch == 0) return rc;
     FeetParamsSet fs = h->feet_set;
     if (!inst_dev) fs.p[0] = h->feet;
@@ -846,6 +852,51 @@ int ismpc_a_rollout_mc_device(ismpc_a_handle* h, int batch, ismpc_a_state* state
     return 0;
 }
 
+// The disturbed closed loop with the swing-foot QPs: ismpc_a_rollout_mc_device's loop over tick_feet.  ismpc_a_feet_kernel reads the
+// tick's f0 and status, so every tick has an output record: its trajectory row, else the handle's scratch records -- whether or not a
+// summary wants them.  (ismpc_a_mc_prologue folds and clears those records in this order when two unrecorded ticks follow each other.)
+int ismpc_a_rollout_mc_feet_device(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, const ismpc_a_inst* inst_dev, int ticks,
+                                   const ismpc_a_push* pushes_dev, int n_push, int traj_stride, ismpc_a_out* traj_dev,
+                                   ismpc_a_rollout_summary* summary_dev, double* feet_dev, ismpc_a_feet_summary* feet_summary_dev, void* stream)
+{
+    if (batch < 0 || ticks < 0) return fail_a(-1, "ismpc_a_rollout_mc_feet_device: negative batch or ticks");
+    if (traj_stride < 1) return fail_a(-1, "ismpc_a_rollout_mc_feet_device: traj_stride must be at least 1");
+    if (n_push < 0) return fail_a(-1, "ismpc_a_rollout_mc_feet_device: negative n_push");
+    if (n_push > 0 && !pushes_dev) return fail_a(-1, "ismpc_a_rollout_mc_feet_device: n_push > 0 with a null push table");
+    if (batch > 0 && !state_dev) return fail_a(-1, "ismpc_a_rollout_mc_feet_device: batch > 0 with a null state");
+    if (batch > 0 && !feet_dev) return fail_a(-1, "ismpc_a_rollout_mc_feet_device: batch > 0 with a null feet_dev");
+    if (!h) return fail_a(-1, "ismpc_a_rollout_mc_feet_device: null handle");
+    ON_DEVICE_A(h);
+    if (h->feet.rows == 0) return fail_a(-1, "feet: call ismpc_a_feet_init_device first and pass an output buffer");
+    if (inst_dev && h->feet_plans == 0) return fail_a(-1, "feet: per-instance batches need ismpc_a_feet_init_inst_device");
+    if (batch == 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ismpc_host::StreamMark<ismpc_a_handle> mark_{h, s};
+    if (batch > h->mc_cap) {                             // stream-ordered growth; ismpc_a_reserve sizes it beforehand
+        ISMPC_GROW_ASYNC(fail_a, h, h->mc, h->mc_cap, batch, MC_BYTES_PER_INSTANCE * (size_t)batch, s);
+    }
+    double* const push = n_push > 0 ? reinterpret_cast<double*>(h->mc + h->mc_cap) : nullptr;
+    ismpc_a_out* last = nullptr;                         // where the previous tick's records are
+    for (int t = 0; t < ticks; ++t) {
+        const bool recorded = traj_dev && (t + 1) % traj_stride == 0;
+        ismpc_a_out* out = recorded ? traj_dev + (size_t)((t + 1) / traj_stride - 1) * batch : h->mc;
+        const McTick mc{pushes_dev, n_push, t, push, summary_dev ? last : nullptr, summary_dev};
+        if (int rc = tick_feet(h, batch, state_dev, inst_dev, push, out, feet_dev, stream, t == 0 ? 1 : 2, &mc)) return rc;
+        last = out;
+    }
+    if (summary_dev) {
+        hipLaunchKernelGGL(ismpc_a_mc_fold, dim3((batch + 255) / 256), dim3(256), 0, s, (const ismpc_a_out*)last, summary_dev, batch, ticks - 1);
+        HIP_TRY_A(hipGetLastError());
+    }
+    if (feet_summary_dev) {
+        hipLaunchKernelGGL(ismpc_a_feet_summary_kernel, dim3((batch + FEET_SUMMARY_WAVES - 1) / FEET_SUMMARY_WAVES), dim3(64 * FEET_SUMMARY_WAVES), 0, s,
+                           (const double*)feet_dev, (const double*)h->feet_base, inst_dev, inst_dev ? std::min(h->feet_plans, h->feet_base_plans) : 1, h->feet.rows, batch,
+                           feet_summary_dev);
+        HIP_TRY_A(hipGetLastError());
+    }
+    return 0;
+}
+
 int ismpc_a_rollout_feet_device(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, int ticks, ismpc_a_out* out_traj_dev,
                                 double* feet_dev, void* stream)
 {
@@ -898,6 +949,31 @@ int ismpc_a_foot_trajectories(const ismpc_a_gait* g, int step, const double* foo
         }
     }
     return n;
+}
+
+// The same on the device for a whole batch (ismpc_a_foot_trajectories_kernel): every instance's refusal is its own nrows = -1.
+int ismpc_a_foot_trajectories_device(ismpc_a_handle* h, int batch, const ismpc_a_inst* inst_dev, const double* feet_dev, int sim_duration,
+                                     double* dst_dev, int32_t* nrows_dev, void* stream)
+{
+    if (batch < 0) return fail_a(-1, "ismpc_a_foot_trajectories_device: negative batch");
+    if (sim_duration < 1) return fail_a(-1, "ismpc_a_foot_trajectories_device: sim_duration must be at least 1");
+    if (batch > 0 && !feet_dev) return fail_a(-1, "ismpc_a_foot_trajectories_device: batch > 0 with a null feet_dev");
+    if (batch > 0 && !dst_dev) return fail_a(-1, "ismpc_a_foot_trajectories_device: batch > 0 with a null dst_dev");
+    if (!h) return fail_a(-1, "ismpc_a_foot_trajectories_device: null handle");
+    ON_DEVICE_A(h);
+    if (h->feet.rows == 0) return fail_a(-1, "feet: call ismpc_a_feet_init_device first and pass an output buffer");
+    if (inst_dev && h->feet_plans == 0) return fail_a(-1, "feet: per-instance batches need ismpc_a_feet_init_inst_device");
+    if (batch == 0) return 0;
+    const int chunks = (sim_duration + FOOT_CHUNK_ROWS - 1) / FOOT_CHUNK_ROWS;
+    if ((long long)batch * chunks > 0x7fffffffLL) return fail_a(-1, "ismpc_a_foot_trajectories_device: batch x sim_duration beyond one launch");
+    const int nplans = inst_dev ? h->feet_plans : 1;
+    FootGaits gaits{};
+    for (int k = 0; k < nplans; ++k) gaits.gait[k] = inst_dev ? h->feet_set.p[k].gait : h->feet.gait;
+    const size_t lds = sizeof(double) * 8 * (size_t)std::min(h->feet.rows, FOOT_PLAN_ROWS);
+    hipLaunchKernelGGL(ismpc_a_foot_trajectories_kernel, dim3(batch * chunks), dim3(FOOT_THREADS), lds, static_cast<hipStream_t>(stream),
+                       gaits, nplans, inst_dev, h->p.step, feet_dev, h->feet.rows, sim_duration, chunks, batch, dst_dev, nrows_dev);
+    HIP_TRY_A(hipGetLastError());
+    return 0;
 }
 
 // fprintf(file, '%d %d %d\n', row): MATLAB prints an integer-valued double with %d and anything else with %e

@@ -39,6 +39,10 @@ ROLLOUT_SUMMARY_A = np.dtype([("status_or", "<i4"), ("first_error_tick", "<i4"),
                               ("max_abs_vel", "<f8", 2), ("max_abs_u0", "<f8", 2)], align=False)
 assert PUSH_A.itemsize == 24 and ROLLOUT_SUMMARY_A.itemsize == 64
 ST_ERROR_MASK_A = ST_X_INFEASIBLE | ST_Y_INFEASIBLE | ST_OVERFLOW | ST_BAD_INDEX      # ISMPC_A_ST_ERROR_MASK = 15
+# the disturbed closed loop with the swing-foot QPs (ismpc_a_rollout_mc_feet_device): an instance's foot plan block against its base plan
+FEET_SUMMARY_A = np.dtype([("moved_rows", "<i4"), ("first_moved_row", "<i4"), ("last_moved_row", "<i4"), ("nonfinite", "<i4"),
+                           ("max_abs_shift", "<f8", 2)], align=False)
+assert FEET_SUMMARY_A.itemsize == 32
 
 EXPORTS_A = ["ismpc_a_params_default", "ismpc_a_gait_default", "ismpc_a_plan", "ismpc_a_create", "ismpc_a_destroy",
              "ismpc_a_initial_state", "ismpc_a_tick_batch_device", "ismpc_a_rollout_device", "ismpc_a_last_error",
@@ -46,7 +50,8 @@ EXPORTS_A = ["ismpc_a_params_default", "ismpc_a_gait_default", "ismpc_a_plan", "
              "ismpc_a_rollout_feet_device", "ismpc_a_foot_trajectories", "ismpc_a_write_trajectory_txt",
              "ismpc_a_add_plan", "ismpc_a_tick_batch_inst_device", "ismpc_a_rollout_inst_device", "ismpc_a_set_warm_history", "ismpc_a_reserve", "ismpc_a_set_precision",
              "ismpc_a_last_deferred", "ismpc_a_feet_init_inst_device", "ismpc_a_tick_feet_batch_inst_device",
-             "ismpc_a_rollout_feet_inst_device", "ismpc_a_rollout_mc_device"]
+             "ismpc_a_rollout_feet_inst_device", "ismpc_a_rollout_mc_device", "ismpc_a_rollout_mc_feet_device",
+             "ismpc_a_foot_trajectories_device"]
 HAVE_F32 = True        # the QP solve also exists in fp32 (GaitGenerator(..., precision="f32"))
 FEET_PAD = 8
 
@@ -84,6 +89,8 @@ def _l():
         lib.ismpc_a_tick_feet_batch_inst_device.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]; lib.ismpc_a_tick_feet_batch_inst_device.restype = ci
         lib.ismpc_a_rollout_feet_inst_device.argtypes = [vp, ci, vp, vp, ci, vp, vp, vp]; lib.ismpc_a_rollout_feet_inst_device.restype = ci
         lib.ismpc_a_rollout_mc_device.argtypes = [vp, ci, vp, vp, ci, vp, ci, ci, vp, vp, vp]; lib.ismpc_a_rollout_mc_device.restype = ci
+        lib.ismpc_a_rollout_mc_feet_device.argtypes = [vp, ci, vp, vp, ci, vp, ci, ci, vp, vp, vp, vp, vp]; lib.ismpc_a_rollout_mc_feet_device.restype = ci
+        lib.ismpc_a_foot_trajectories_device.argtypes = [vp, ci, vp, vp, ci, vp, vp, vp]; lib.ismpc_a_foot_trajectories_device.restype = ci
         _bound = True
     return lib
 
@@ -221,6 +228,64 @@ class GaitGenerator:
                                pushes.data_ptr() if n_push else None, n_push, stride,
                                traj.data_ptr() if want_traj else None, summary.data_ptr() if want_summary else None, stream)
         return traj, summary
+
+    def rollout_mc_feet_device(self, batch, state_ptr, feet_ptr, ticks, inst_ptr=None, pushes_ptr=None, n_push=0, stride=1, traj_ptr=None,
+                               summary_ptr=None, feet_summary_ptr=None, stream=None):
+        """ismpc_a_rollout_mc_feet_device on raw device pointers: rollout_mc_device with the swing-foot QP of every instance behind every
+        tick (feet_ptr: batch x feet_rows x 8 doubles, in place) and one ismpc_a_feet_summary per instance behind the last one."""
+        opt = lambda p: C.c_void_p(p) if p else None
+        rc = _l().ismpc_a_rollout_mc_feet_device(self._h, int(batch), opt(state_ptr), opt(inst_ptr), int(ticks), opt(pushes_ptr), int(n_push),
+                                                 int(stride), opt(traj_ptr), opt(summary_ptr), opt(feet_ptr), opt(feet_summary_ptr), opt(stream))
+        if rc != 0:
+            raise IsmpcAError(_l().ismpc_a_last_error().decode())
+
+    def rollout_mc_feet_torch(self, state_u8, feet, ticks, pushes=None, stride=1, want_traj=True, want_summary=True, want_feet_summary=True,
+                              inst_u8=None):
+        """The disturbed closed loop with the swing-foot QPs on torch tensors.  state_u8, pushes, inst_u8: as rollout_mc_torch; feet: the
+        CUDA float64 [batch, feet_rows, 8] block of feet_init_torch / feet_init_inst_torch, updated in place.  Returns (traj, summary,
+        feet_summary): as rollout_mc_torch, and CUDA uint8 [batch, 32] (FEET_SUMMARY_A: the block as it stands against the base plan) or None."""
+        import torch
+        b = state_u8.shape[0]
+        assert state_u8.is_cuda and state_u8.dtype == torch.uint8 and state_u8.shape[1] == 96 and state_u8.is_contiguous()
+        n_push = 0
+        if pushes is not None:
+            assert pushes.is_cuda and pushes.dtype == torch.uint8 and pushes.dim() == 3 and pushes.shape[0] == b and pushes.shape[2] == 24 and pushes.is_contiguous()
+            assert pushes.device == state_u8.device
+            n_push = int(pushes.shape[1])
+        if inst_u8 is not None:
+            assert inst_u8.is_cuda and inst_u8.dtype == torch.uint8 and inst_u8.shape == (b, 32) and inst_u8.is_contiguous()
+        assert feet.is_cuda and feet.dtype == torch.float64 and feet.is_contiguous() and feet.device == state_u8.device
+        assert tuple(feet.shape) == (b, _l().ismpc_a_feet_rows(self._h), 8)
+        traj = torch.empty((ticks // stride if stride >= 1 else 0, b, 80), dtype=torch.uint8, device=state_u8.device) if want_traj else None
+        summary = torch.empty((b, 64), dtype=torch.uint8, device=state_u8.device) if want_summary else None
+        feet_summary = torch.empty((b, 32), dtype=torch.uint8, device=state_u8.device) if want_feet_summary else None
+        stream = torch.cuda.current_stream(state_u8.device).cuda_stream
+        self.rollout_mc_feet_device(b, state_u8.data_ptr(), feet.data_ptr(), ticks, inst_u8.data_ptr() if inst_u8 is not None else None,
+                                    pushes.data_ptr() if n_push else None, n_push, stride, traj.data_ptr() if want_traj else None,
+                                    summary.data_ptr() if want_summary else None, feet_summary.data_ptr() if want_feet_summary else None, stream)
+        return traj, summary, feet_summary
+
+    def foot_trajectories_torch(self, feet, sim_duration, inst_u8=None):
+        """The four foot files of every instance on the device (ismpc_a_foot_trajectories_device), bit for bit foot_trajectories() of the
+        instance's rows of `feet` (CUDA float64 [batch, feet_rows, 8]).  inst_u8: None (the handle's step and plan 0) or CUDA uint8
+        [batch, 32] INST_A records (step and base plan per instance).  Returns (files, nrows): CUDA float64 [batch, 4, sim_duration, 3] in
+        the order fl, fr, rl, rr, and CUDA int32 [batch] with n_b = (sim_duration // step_b) * step_b, or -1 where foot_trajectories()
+        would raise.  `files` is uninitialised memory: rows at and after nrows[b] (all rows where nrows[b] == -1) are unspecified."""
+        import torch
+        b = feet.shape[0]
+        assert feet.is_cuda and feet.dtype == torch.float64 and feet.is_contiguous()
+        assert tuple(feet.shape) == (b, _l().ismpc_a_feet_rows(self._h), 8)
+        if inst_u8 is not None:
+            assert inst_u8.is_cuda and inst_u8.dtype == torch.uint8 and inst_u8.shape == (b, 32) and inst_u8.is_contiguous() and inst_u8.device == feet.device
+        files = torch.empty((b, 4, max(int(sim_duration), 0), 3), dtype=torch.float64, device=feet.device)
+        nrows = torch.empty((b,), dtype=torch.int32, device=feet.device)
+        stream = torch.cuda.current_stream(feet.device).cuda_stream
+        opt = lambda p: C.c_void_p(p) if p else None
+        rc = _l().ismpc_a_foot_trajectories_device(self._h, b, opt(inst_u8.data_ptr() if inst_u8 is not None else None), opt(feet.data_ptr()),
+                                                   int(sim_duration), opt(files.data_ptr()), opt(nrows.data_ptr()), opt(stream))
+        if rc != 0:
+            raise IsmpcAError(_l().ismpc_a_last_error().decode())
+        return files, nrows
 
     def reserve(self, max_batch):
         """Sizes the handle's scratch for batches up to max_batch now (ismpc_a_reserve) instead of stream-ordered inside the calls."""
