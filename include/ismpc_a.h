@@ -94,7 +94,7 @@ typedef struct ismpc_a_inst {
     double  Qf;                         /* Qfootsteps */
     int32_t step, ds;                   /* step_duration, dsSamples */
     int32_t F;                          /* footsteps in this instance's horizon, 1 <= F <= ismpc_a_params.F of the handle */
-    int32_t plan;                       /* base plan: 0 = the one given to ismpc_a_create, k = k-th ismpc_a_add_plan */
+    int32_t plan;                       /* base plan: 0 = the one given to ismpc_a_create, k = k-th ismpc_a_add_plan; or the index into a plan table */
 } ismpc_a_inst;
 
 typedef struct ismpc_a_handle ismpc_a_handle;
@@ -150,6 +150,37 @@ int ismpc_a_tick_batch_inst_device(ismpc_a_handle* h, int batch, ismpc_a_state* 
                                    const double* push_dev, ismpc_a_out* out_dev, void* stream);
 int ismpc_a_rollout_inst_device(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, const ismpc_a_inst* inst_dev,
                                 int ticks, ismpc_a_out* out_traj_dev, void* stream);
+
+/* ---- PLAN-TABLE handles: any number of base plans, built on the device.
+ * ismpc_a_create_plans takes n_plans gait records (host) instead of one centre.  Plan 0 is gaits[0]: everything ismpc_a_create builds
+ * from `center` (centreline tables, tails, the plan of the plain launches) is built from the host's ismpc_a_plan(&gaits[0]), so every
+ * entry point that takes no ismpc_a_inst behaves exactly as on ismpc_a_create(p, that centre).  All n_plans plans, plan 0 included, are
+ * generated by ONE launch on the device into a table the handle owns -- per plan the centre (n_gait x values in the x table, n_gait y
+ * values in the y table: the layout the tick kernel's `fs` reads), the foot plan ((n_gait + 1 + ISMPC_A_FEET_PAD) x 8, the last plan row
+ * repeated behind the plan) and the foot rules -- bit for bit what ismpc_a_plan writes for the same record.  An instance names its plan
+ * in ismpc_a_inst.plan, 0 <= plan < n_plans; any other value gets ISMPC_A_ST_BAD_INDEX and the instance is left alone.
+ * Every gaits[k] needs n_gait == p->n_gait and gait 0 (trot) or 1 (walk); the two may mix.  1 <= n_plans <= ISMPC_A_MAX_PLANS: the
+ * limit keeps 8 n_plans (the generator's thread index) inside an int32; the table takes 80 n_gait + 616 bytes per plan
+ * (8616 bytes at n_gait = 100) and the handle 64 bytes of host memory per plan.
+ * Returns -1 before the device is touched, ismpc_a_last_error naming the function and the argument: null p / gaits / out, n_plans < 1
+ * or beyond the limit, p->n_gait < 16, a record whose n_gait differs, an unknown gait kind; then ismpc_a_create's own errors.
+ * ismpc_a_add_plan and ismpc_a_feet_init_inst_device return -1 on such a handle (the table is the source of plans and foot plans). */
+#define ISMPC_A_MAX_PLANS 0x0fffffff
+int ismpc_a_create_plans(const ismpc_a_params* p, const ismpc_a_gait* gaits, int n_plans, int device, ismpc_a_handle** out);
+/* base plans of the handle: n_plans of ismpc_a_create_plans, or 1 + the ismpc_a_add_plan calls of an ismpc_a_create handle */
+int ismpc_a_plans_info(const ismpc_a_handle* h, int* n_plans);
+/* milliseconds the generator launch of ismpc_a_create_plans took on the device (HIP events around it); -1: not a plan-table handle */
+double ismpc_a_plans_build_ms(const ismpc_a_handle* h);
+/* Plan `plan` of a plan-table handle, read back from the device: ismpc_a_plan's outputs (either pointer may be NULL) and its return value. */
+int ismpc_a_get_plan(ismpc_a_handle* h, int plan, double* foot_plan, double* center);
+/* ismpc_a_initial_state for plan `plan` of a plan-table handle: x = xz = disp_C / 2 of that plan's gait record, the current footstep =
+ * the plan's first centre (quad_walk_no_plots.m:52-62). */
+int ismpc_a_initial_state_plan(const ismpc_a_handle* h, int plan, ismpc_a_state* st);
+/* Host: the transcendental part of ismpc_a_plan -- the clipped step (x, y) and first half step (x, y) of init_quadruped*.m:55-102, in
+ * the order xs, ys, xsd, ysd.  ismpc_a_plan and ismpc_a_create_plans both call it; the rest of a plan is additions and the IEEE
+ * divisions of the diagonal intersections.  Returns which clip branches ran: 1 = half step lateral, 2 = half step forward,
+ * 4 = step lateral, 8 = step forward (or a negative error). */
+int ismpc_a_plan_steps(const ismpc_a_gait* g, double steps[4]);
 
 /* DISTURBED closed loop with per-instance summaries: the tick loop of ismpc_a_rollout_device (inst_dev = NULL: the handle's
  * parameters) or ismpc_a_rollout_inst_device (batch records) -- same working-set history, same behaviour on error ticks: the loop goes
@@ -241,6 +272,12 @@ int ismpc_a_rollout_feet_device(ismpc_a_handle* h, int batch, ismpc_a_state* sta
  * with its own step_duration.                                                                                          */
 int ismpc_a_feet_init_inst_device(ismpc_a_handle* h, const ismpc_a_gait* gaits, const double* foot_plans_host, int rows,
                                   int nplans, int batch, const ismpc_a_inst* inst_dev, double* feet_dev, void* stream);
+/* The same start on a plan-table handle (ismpc_a_create_plans): every instance's block is filled from the TABLE's foot plan of its plan
+ * (inst_dev NULL: plan 0 for every instance; an unknown index: plan 0, as above); no host foot plan is involved.  rows: plan rows per
+ * instance as above, 2 <= rows <= n_gait + 1 (the table holds n_gait + 1 plan rows: a trot plan's last row twice); the block is
+ * rows + ISMPC_A_FEET_PAD rows.  Afterwards every feet entry point (tick_feet_batch[_inst], rollout_feet[_inst], rollout_mc_feet,
+ * foot_trajectories_device) works on the handle with its documented meaning, for any plan index of the table. */
+int ismpc_a_feet_init_plans_device(ismpc_a_handle* h, int rows, int batch, const ismpc_a_inst* inst_dev, double* feet_dev, void* stream);
 int ismpc_a_tick_feet_batch_inst_device(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, const ismpc_a_inst* inst_dev,
                                         const double* push_dev, ismpc_a_out* out_dev, double* feet_dev, void* stream);
 int ismpc_a_rollout_feet_inst_device(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, const ismpc_a_inst* inst_dev,

@@ -24,7 +24,9 @@ struct DevA {
     const double *fsx, *fsy;           // base plan, 0-based (fs_plan(k+1))
     const double *clx0, *cly0, *clx1, *cly1;   // centreline: initial / rebuilt structure, 0-based (cl(k+1))
     double* scratch;                   // per-workgroup S^-1 : ldq x ldq doubles each
-    const double *plan_x[4], *plan_y[4]; int nplans; double grav;   // base plans selectable per instance (ismpc_a_inst.plan)
+    // base plans selectable per instance (ismpc_a_inst.plan): plan k's centre is the n_gait doubles at tab_x + k n_gait and tab_y + k n_gait
+    // (ismpc_a_create / ismpc_a_add_plan: a table of four; ismpc_a_create_plans: the table the generator kernel wrote, ismpc_a_plans.hpp)
+    const double *tab_x, *tab_y; int nplans; double grav;
     // anticipative tail of the handle's own gait parameters as a function of the tick index alone (quad_walk_no_plots.m:227-231):
     // T[j] = sum_{i=C+1..P} wtail_i cl(j+i) + wP cl(P), per centreline table; the tail of a tick is T[j] + (offset - current footstep) sumw
     const double *tlx0, *tly0, *tlx1, *tly1;

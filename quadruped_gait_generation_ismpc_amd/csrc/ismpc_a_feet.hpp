@@ -11,7 +11,11 @@ namespace {
 // minimiser is the projection of the target on the box).  trotting/quad_as_bip_no_plots.m:332-426 + compute_two_feet1.m,
 // walking/quad_walk_no_plots.m:336-504 + compute_one_feet_walk.m:84-140.
 struct FeetParams { int gait, rows; double phi, disp_i, disp_o, disp_forw; };
-struct FeetParamsSet { FeetParams p[4]; };           // per base plan (ismpc_a_inst.plan): Monte-Carlo batches mix trot and walk instances
+struct FeetParamsSet { FeetParams p[4]; };           // per base plan (ismpc_a_inst.plan) of an ismpc_a_create handle: host copy of its rules
+// What the feet kernels read per base plan, in device memory, for ANY plan index below nplans: the foot rules (FeetParams; its `rows` is
+// the table's, the kernels take the instance block's row count as an argument) and the base foot plans, base_rows x 8 doubles per plan.
+// An instance block of `rows` rows (plan rows + ISMPC_A_FEET_PAD) starts as base rows 0 .. rows - 9 with the last of them repeated.
+struct FeetTab { const FeetParams* rules; const double* base; int nplans, base_rows; };
 
 __device__ __forceinline__ void fixed_diagonal(double fx1, double fy1, double fx2, double fy2, double zx, double zy,
                                                double& m, double& dx, double& dy)
@@ -23,18 +27,18 @@ __device__ __forceinline__ void fixed_diagonal(double fx1, double fy1, double fx
 }
 __device__ __forceinline__ double clipd(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-__global__ void ismpc_a_feet_kernel(const FeetParamsSet fset, const ismpc_a_inst* __restrict__ inst, int nplans, const ismpc_a_state* __restrict__ prev,
-                                    const ismpc_a_out* __restrict__ out, double* __restrict__ feet, int batch)
+__global__ void ismpc_a_feet_kernel(const FeetTab tab, const ismpc_a_inst* __restrict__ inst, const ismpc_a_state* __restrict__ prev,
+                                    const ismpc_a_out* __restrict__ out, double* __restrict__ feet, int rows, int batch)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= batch) return;
     if (out[b].status & (ISMPC_A_ST_BAD_INDEX | ISMPC_A_ST_OVERFLOW)) return;
     int pl = inst ? inst[b].plan : 0;                            // per-instance gait parameters: the foot rules of the instance's base plan
-    if (pl < 0 || pl >= nplans) return;
-    const FeetParams fpz = fset.p[pl];
+    if (pl < 0 || pl >= tab.nplans) return;
+    const FeetParams fpz = tab.rules[pl];
     const int fc = prev[b].fc;                                   // the fsCounter this tick ran with
-    if (fc < 1 || fc + 8 >= fpz.rows) return;                    // end-of-plan rule of ismpc_a.h: rows fc+1 .. fc+8 stay inside the instance's block
-    double* fp = feet + (size_t)b * fpz.rows * 8;
+    if (fc < 1 || fc + 8 >= rows) return;                    // end-of-plan rule of ismpc_a.h: rows fc+1 .. fc+8 stay inside the instance's block
+    double* fp = feet + (size_t)b * rows * 8;
 #define FPL(r, c) fp[(size_t)((r) - 1) * 8 + ((c) - 1)]
     const double zx = out[b].f0[0], zy = out[b].f0[1];           // predicted_xfs(1), predicted_yfs(1)
     const double di = fpz.disp_i, dob = fpz.disp_o, df = fpz.disp_forw;
@@ -96,14 +100,15 @@ __global__ void ismpc_a_feet_fill(const double* __restrict__ base, double* __res
     const size_t n = (size_t)batch * rows * 8;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) feet[e] = base[e % ((size_t)rows * 8)];
 }
-// every instance starts from the foot plan of ITS base plan (base: nplans x rows x 8)
-__global__ void ismpc_a_feet_fill_inst(const double* __restrict__ base, const ismpc_a_inst* __restrict__ inst, int nplans, double* __restrict__ feet, int rows, int batch)
+// every instance starts from the foot plan of ITS base plan (FeetTab; inst NULL: plan 0): plan rows 0 .. rows - 9, the last one repeated
+__global__ void ismpc_a_feet_fill_inst(const FeetTab tab, const ismpc_a_inst* __restrict__ inst, double* __restrict__ feet, int rows, int batch)
 {
     const size_t per = (size_t)rows * 8, n = (size_t)batch * per;
+    const size_t last = (size_t)(rows - ISMPC_A_FEET_PAD - 1) * 8;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
-        const size_t b = e / per;
-        int pl = inst[b].plan; if (pl < 0 || pl >= nplans) pl = 0;
-        feet[e] = base[(size_t)pl * per + (e - b * per)];
+        const size_t b = e / per, k = e - b * per;
+        int pl = inst ? inst[b].plan : 0; if (pl < 0 || pl >= tab.nplans) pl = 0;
+        feet[e] = tab.base[(size_t)pl * tab.base_rows * 8 + (k < last ? k : last + (k & 7))];
     }
 }
 

@@ -16,24 +16,24 @@ namespace {
 constexpr int FEET_SUMMARY_WAVES = 4;
 
 __global__ void __launch_bounds__(64 * FEET_SUMMARY_WAVES)
-ismpc_a_feet_summary_kernel(const double* __restrict__ feet, const double* __restrict__ base, const ismpc_a_inst* __restrict__ inst, int nplans,
+ismpc_a_feet_summary_kernel(const double* __restrict__ feet, const FeetTab tab, const ismpc_a_inst* __restrict__ inst,
                             int rows, int batch, ismpc_a_feet_summary* __restrict__ summary)
 {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * FEET_SUMMARY_WAVES + (threadIdx.x >> 6);        // wave-uniform
     if (b >= batch) return;
     int pl = inst ? inst[b].plan : 0;
-    if (pl < 0 || pl >= nplans) pl = 0;                                         // what ismpc_a_feet_fill_inst gave the instance
-    const int n = rows * 8;
+    if (pl < 0 || pl >= tab.nplans) pl = 0;                                     // what ismpc_a_feet_fill_inst gave the instance
+    const int n = rows * 8, tail = (rows - ISMPC_A_FEET_PAD - 1) * 8;           // the base plan's last row stands behind it (FeetTab)
     const double* f = feet + (size_t)b * n;
-    const double* g = base + (size_t)pl * n;
+    const double* g = tab.base + (size_t)pl * tab.base_rows * 8;
     int moved = 0, first = 0, last = 0, nonfinite = 0;                          // wave-uniform
     double shift = 0.0;                                                         // this lane's column
     for (int e0 = 0; e0 < n; e0 += 64) {
         const int e = e0 + lane;
         bool differs = false, bad = false;
         if (e < n) {
-            const double v = f[e], w = g[e];
+            const double v = f[e], w = g[e < tail ? e : tail + (e & 7)];
             differs = !(v == w);
             bad = !isfinite(v);
             shift = fmax(shift, fabs(v - w));                                   // fmax: a NaN difference leaves the maximum as it is
@@ -84,10 +84,8 @@ constexpr int FOOT_CHUNK_ROWS = 512;
 constexpr int FOOT_THREADS = 256;
 constexpr int FOOT_PLAN_ROWS = FOOT_CHUNK_ROWS + 2;                             // a chunk's rows span (FOOT_CHUNK_ROWS - 1) / step + 3 plan rows at the most
 
-struct FootGaits { int gait[4]; };           // per base plan: 0 = trot, 1 = walk
-
 __global__ void __launch_bounds__(FOOT_THREADS)
-ismpc_a_foot_trajectories_kernel(FootGaits gaits, int nplans, const ismpc_a_inst* __restrict__ inst, int step_h, const double* __restrict__ feet,
+ismpc_a_foot_trajectories_kernel(const FeetTab tab, const ismpc_a_inst* __restrict__ inst, int step_h, const double* __restrict__ feet,
                                  int rows, int sim_duration, int chunks, int batch, double* __restrict__ dst, int32_t* __restrict__ nrows)
 {
     extern __shared__ double plan[];                                            // the plan rows of this chunk x 8 (FOOT_PLAN_ROWS at the most)
@@ -96,10 +94,10 @@ ismpc_a_foot_trajectories_kernel(FootGaits gaits, int nplans, const ismpc_a_inst
     const int step = inst ? inst[b].step : step_h;
     const int pl = inst ? inst[b].plan : 0;
     // the host function's refusals: the instance writes nothing
-    bool ok = step >= 1 && sim_duration >= step && pl >= 0 && pl < nplans;
+    bool ok = step >= 1 && sim_duration >= step && pl >= 0 && pl < tab.nplans;
     int nsteps = 0, n = 0, gait = 0;
     if (ok) {
-        nsteps = sim_duration / step; n = nsteps * step; gait = gaits.gait[pl];
+        nsteps = sim_duration / step; n = nsteps * step; gait = tab.rules[pl].gait;                  // per base plan: 0 = trot, 1 = walk
         ok = nsteps + 1 <= rows && !(gait == 0 && step <= 50);
     }
     if (chunk == 0 && threadIdx.x == 0 && nrows) nrows[b] = ok ? n : -1;

@@ -9,12 +9,15 @@
 //   ismpc_a_feet.hpp        ismpc_a_feet_kernel (swing-foot re-placement after a tick), ismpc_a_feet_fill, ismpc_a_feet_fill_inst
 //   ismpc_a_feet_files.hpp  ismpc_a_feet_summary_kernel (a batch's foot plans against the base plans), ismpc_a_foot_trajectories_kernel (the
 //                           four foot files of every instance, the host writer's bits)
+//   ismpc_a_plans.hpp       ismpc_a_plan_table_kernel (the plan generators on the device: every plan of a plan-table handle in one launch,
+//                           the host's ismpc_a_plan to the bit)
 //   ismpc_wave_prims.hpp    wavefront prefix sum (shared with Formulation B)
 //   ismpc_host.hpp          device guard, early return on a HIP error, growth of scratch (shared by the three ABIs)
 //   this file               the error string; host geometry (linspace_m, centreline, ismpc_a_plan, ismpc_a_foot_trajectories, the text
 //                           writer); ismpc_a_handle and its run-time knobs; the launch path (ismpc_a_tick_prologue, ismpc_a_bucket_by_F,
 //                           tick_launch, tick_feet, rollout_a); the disturbed closed loop (ismpc_a_mc_prologue, ismpc_a_mc_fold,
-//                           ismpc_a_rollout_mc_device, ismpc_a_rollout_mc_feet_device); ismpc_a_foot_trajectories_device; the extern "C"
+//                           ismpc_a_rollout_mc_device, ismpc_a_rollout_mc_feet_device); ismpc_a_foot_trajectories_device; plan-table handles
+//                           (ismpc_a_plan_steps, build_plan_table, ismpc_a_create_plans, ismpc_a_feet_init_plans_device); the extern "C"
 //                           entry points
 //
 // Results are the unique minimiser: validated against the oracle's null-space Goldfarb-Idnani and the
@@ -35,6 +38,7 @@
 #include "ismpc_a_block.hpp"
 #include "ismpc_a_feet.hpp"
 #include "ismpc_a_feet_files.hpp"
+#include "ismpc_a_plans.hpp"
 
 namespace {
 
@@ -82,6 +86,18 @@ struct ismpc_a_handle {
     FeetParams feet{}; double* feet_base = nullptr;     // swing-foot QPs (ismpc_a_feet_init_device)
     int feet_base_plans = 0;                             // base plans feet_base holds (feet_upload): what ismpc_a_feet_summary_kernel may index
     FeetParamsSet feet_set{}; int feet_plans = 0;        // ... and per base plan (ismpc_a_feet_init_inst_device)
+    FeetParams* feet_rules = nullptr;                    // device copy of both: [0, 4) feet_set.p, [4] feet (what the feet kernels read: FeetTab)
+    double* plan_tab = nullptr;                          // ismpc_a_create: the centres of up to four base plans (c.tab_x, c.tab_y point into it)
+    // plan-table handles (ismpc_a_create_plans): the table the generator kernel wrote (c.tab_x / c.tab_y are its centres) and the records
+    bool table = false; double* tab_feet = nullptr; FeetParams* tab_rules = nullptr; float build_ms = 0.0f;
+    bool feet_from_table = false;                        // plain feet launches read plan 0 of the table (ismpc_a_feet_init_plans_device), not feet_base
+    std::vector<ismpc_a_gait> gaits;
+    // what the feet kernels read: per-instance launches any plan of the handle, plain launches plan 0 (the rules of ismpc_a_feet_init_device)
+    FeetTab feet_tab(bool per_inst) const
+    {
+        if (table && (per_inst || feet_from_table)) return FeetTab{tab_rules, tab_feet, per_inst ? c.nplans : 1, plan_table_rows(p.n_gait)};
+        return per_inst ? FeetTab{feet_rules, feet_base, feet_plans, feet.rows} : FeetTab{feet_rules + 4, feet_base, 1, feet.rows};
+    }
     bool use_wave = true; int wave_blocks = 0;           // structured wavefront-per-QP kernel (default) vs workgroup-per-QP
     int cus = 0, wave_occ[16] = {0};                     // resident workgroups per CU of the wave kernels ([F - 3][precision x per-instance])
     ismpc_a::PiPre* pre = nullptr; int pre_cap = 0;       // per-instance launches: the prologue's record per instance
@@ -311,22 +327,35 @@ void ismpc_a_gait_default(int gait, double phi, double disp_A, ismpc_a_gait* g)
     g->disp_B = 0.259394; g->disp_C = 0.88; g->disp_i = 0.4; g->disp_o = 0.4; g->disp_forw = 0.5;
 }
 
+// The step and the first (half) step of a plan, clipped to the kinematic limits (init_quadruped*.m:55-102): everything in a plan that
+// takes cos, sin or atan.  ismpc_a_plan and ismpc_a_create_plans (whose generator kernel gets these four doubles per plan) share it.
+int ismpc_a_plan_steps(const ismpc_a_gait* g, double steps[4])
+{
+    if (!g || !steps) return fail_a(-1, "ismpc_a_plan_steps: null argument");
+    const double dfd = g->disp_forw / 2, dv = std::min(g->disp_i, g->disp_o), dvd = dv / 2;
+    double xs = g->disp_A * std::cos(g->phi), ys = g->disp_A * std::sin(g->phi);
+    double xsd = g->disp_A * std::cos(g->phi) / 2, ysd = g->disp_A * std::sin(g->phi) / 2;
+    int branches = 0;
+    auto clip = [&](double& x, double& y, double vlim, double flim, int bit) {
+        if (y > vlim || x > flim) {
+            if (g->phi > std::atan(vlim / flim)) { y = vlim; x = vlim * std::cos(g->phi) / std::sin(g->phi); branches |= bit; }
+            else { x = flim; y = flim * std::sin(g->phi) / std::cos(g->phi); branches |= 2 * bit; }
+        }
+    };
+    clip(xsd, ysd, dvd, dfd, 1);          // first (half) step   :62-81
+    clip(xs, ys, dv, g->disp_forw, 4);    // regular step        :84-102
+    steps[0] = xs; steps[1] = ys; steps[2] = xsd; steps[3] = ysd;
+    return branches;
+}
+
 // trotting/init_quadruped.m:5-184, walking/init_quadruped2.m:5-284 (host; once per run)
 int ismpc_a_plan(const ismpc_a_gait* g, double* foot_plan, double* center)
 {
     if (!g || !foot_plan || !center || g->n_gait < 16) return fail_a(-1, "bad argument");
     const int NG = g->n_gait;
-    const double dfd = g->disp_forw / 2, dv = std::min(g->disp_i, g->disp_o), dvd = dv / 2;
-    double xs = g->disp_A * std::cos(g->phi), ys = g->disp_A * std::sin(g->phi);
-    double xsd = g->disp_A * std::cos(g->phi) / 2, ysd = g->disp_A * std::sin(g->phi) / 2;
-    auto clip = [&](double& x, double& y, double vlim, double flim) {
-        if (y > vlim || x > flim) {
-            if (g->phi > std::atan(vlim / flim)) { y = vlim; x = vlim * std::cos(g->phi) / std::sin(g->phi); }
-            else { x = flim; y = flim * std::sin(g->phi) / std::cos(g->phi); }
-        }
-    };
-    clip(xsd, ysd, dvd, dfd);          // first (half) step   :62-81
-    clip(xs, ys, dv, g->disp_forw);    // regular step        :84-102
+    double steps[4];
+    ismpc_a_plan_steps(g, steps);
+    const double xs = steps[0], ys = steps[1], xsd = steps[2], ysd = steps[3];
     const int rows = NG + 1;           // 1-based rows 1..NG+1 stored at index row-1
     std::vector<double> fp((size_t)(rows + 8) * 8);
     auto FP = [&](int r, int col) -> double& { return fp[(size_t)(r - 1) * 8 + (col - 1)]; };
@@ -371,9 +400,10 @@ int ismpc_a_plan(const ismpc_a_gait* g, double* foot_plan, double* center)
             used = std::max(used, j + 7);
         }
         used = std::min(used, NG + 1);
+        // (for some NG, 23 among them, the script's array grows past row NG; the caller's `center` has NG rows: those rows are not written)
         for (int j = 1; j <= NG - 4; j += 8) {
-            for (int k = 0; k <= 6; k += 2) cross(j + k, center[(j+k-1)*2], center[(j+k-1)*2+1]);
-            for (int k = 1; k <= 7; k += 2) { center[(j+k-1)*2] = center[(j+k-2)*2]; center[(j+k-1)*2+1] = center[(j+k-2)*2+1]; }
+            for (int k = 0; k <= 6; k += 2) if (j + k <= NG) cross(j + k, center[(j+k-1)*2], center[(j+k-1)*2+1]);
+            for (int k = 1; k <= 7; k += 2) if (j + k <= NG) { center[(j+k-1)*2] = center[(j+k-2)*2]; center[(j+k-1)*2+1] = center[(j+k-2)*2+1]; }
         }
     }
     std::memcpy(foot_plan, fp.data(), sizeof(double) * (size_t)used * 8);
@@ -459,7 +489,15 @@ int ismpc_a_create(const ismpc_a_params* p, const double* center, int device, is
     if (!rc) rc = upload_a(h, wt, &c.wtail);
     if (!rc) rc = upload_a(h, h->fsx, &c.fsx);
     if (!rc) rc = upload_a(h, h->fsy, &c.fsy);
-    if (!rc) { c.plan_x[0] = c.fsx; c.plan_y[0] = c.fsy; c.nplans = 1; c.grav = p->grav; }
+    if (!rc) {
+        // the centres of the base plans per-instance launches choose from: four slots of n_gait x values, then four of n_gait y values
+        std::vector<double> tab((size_t)8 * p->n_gait, 0.0);
+        std::copy(h->fsx.begin(), h->fsx.end(), tab.begin());
+        std::copy(h->fsy.begin(), h->fsy.end(), tab.begin() + (size_t)4 * p->n_gait);
+        const double* t0 = nullptr;
+        rc = upload_a(h, tab, &t0);
+        if (!rc) { h->plan_tab = const_cast<double*>(t0); c.tab_x = t0; c.tab_y = t0 + (size_t)4 * p->n_gait; c.nplans = 1; c.grav = p->grav; }
+    }
     if (!rc) rc = upload_a(h, clx0, &c.clx0);
     if (!rc) rc = upload_a(h, cly0, &c.cly0);
     if (!rc) rc = upload_a(h, clx1, &c.clx1);
@@ -527,17 +565,137 @@ int ismpc_a_initial_state(const ismpc_a_handle* h, double disp_C, ismpc_a_state*
 int ismpc_a_add_plan(ismpc_a_handle* h, const double* center)
 {
     if (!h || !center) return fail_a(-1, "null argument");
+    if (h->table) return fail_a(-1, "ismpc_a_add_plan: the plans of a plan-table handle are those given to ismpc_a_create_plans");
     if (h->c.nplans >= 4) return fail_a(-1, "at most 4 base plans per handle");
     ON_DEVICE_A(h);
-    std::vector<double> px(h->p.n_gait), py(h->p.n_gait);
-    for (int i = 0; i < h->p.n_gait; ++i) { px[i] = center[i * 2]; py[i] = center[i * 2 + 1]; }
+    const int NG = h->p.n_gait;
+    std::vector<double> px(NG), py(NG);
+    for (int i = 0; i < NG; ++i) { px[i] = center[i * 2]; py[i] = center[i * 2 + 1]; }
     const int k = h->c.nplans;
-    int rc = upload_a(h, px, &h->c.plan_x[k]);
-    if (!rc) rc = upload_a(h, py, &h->c.plan_y[k]);
-    if (rc) return rc;
+    HIP_TRY_A(hipMemcpy(h->plan_tab + (size_t)k * NG, px.data(), sizeof(double) * NG, hipMemcpyHostToDevice));
+    HIP_TRY_A(hipMemcpy(h->plan_tab + (size_t)(4 + k) * NG, py.data(), sizeof(double) * NG, hipMemcpyHostToDevice));
     h->c.nplans = k + 1;
     HIP_TRY_A(hipMemcpy(h->c_dev, &h->c, sizeof(DevA), hipMemcpyHostToDevice));
     return k;
+}
+
+// ---- plan-table handles
+namespace {
+struct DevTemp { void* p = nullptr; ~DevTemp() { if (p) (void)hipFree(p); } };   // device memory of one call
+
+// All plans of `gaits` into one table on the handle's device (the current one), by one launch of ismpc_a_plan_table_kernel.
+int build_plan_table(ismpc_a_handle* h, const ismpc_a_gait* gaits, int n_plans)
+{
+    const int NG = h->p.n_gait, FR = plan_table_rows(NG);
+    std::vector<double> steps((size_t)n_plans * 4);
+    for (int k = 0; k < n_plans; ++k) ismpc_a_plan_steps(&gaits[k], &steps[(size_t)k * 4]);
+    h->gaits.assign(gaits, gaits + n_plans);
+    void *centres = nullptr, *feet = nullptr, *rules = nullptr;
+    HIP_TRY_A(hipMalloc(&centres, sizeof(double) * 2 * (size_t)n_plans * NG)); h->allocs.push_back(centres);
+    HIP_TRY_A(hipMalloc(&feet, sizeof(double) * 8 * (size_t)n_plans * FR)); h->allocs.push_back(feet);
+    HIP_TRY_A(hipMalloc(&rules, sizeof(FeetParams) * (size_t)n_plans)); h->allocs.push_back(rules);
+    DevTemp g_dev, s_dev;
+    HIP_TRY_A(hipMalloc(&g_dev.p, sizeof(ismpc_a_gait) * (size_t)n_plans));
+    HIP_TRY_A(hipMalloc(&s_dev.p, sizeof(double) * 4 * (size_t)n_plans));
+    HIP_TRY_A(hipMemcpy(g_dev.p, gaits, sizeof(ismpc_a_gait) * (size_t)n_plans, hipMemcpyHostToDevice));
+    HIP_TRY_A(hipMemcpy(s_dev.p, steps.data(), sizeof(double) * 4 * (size_t)n_plans, hipMemcpyHostToDevice));
+    double* tx = static_cast<double*>(centres);
+    double* ty = tx + (size_t)n_plans * NG;
+    hipEvent_t e0 = nullptr, e1 = nullptr;                         // the launch's own time (ismpc_a_plans_build_ms)
+    HIP_TRY_A(hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail_a(-2, "hipEventCreate failed"); }
+    (void)hipEventRecord(e0, nullptr);
+    const unsigned grid = (unsigned)(((size_t)n_plans * 8 + PLAN_GEN_THREADS - 1) / PLAN_GEN_THREADS);
+    hipLaunchKernelGGL(ismpc_a_plan_table_kernel, dim3(grid), dim3(PLAN_GEN_THREADS), 0, nullptr, (const ismpc_a_gait*)g_dev.p, (const double*)s_dev.p,
+                       n_plans, NG, tx, ty, static_cast<double*>(feet), static_cast<FeetParams*>(rules));
+    hipError_t err = hipGetLastError();
+    (void)hipEventRecord(e1, nullptr);
+    if (err == hipSuccess) err = hipEventSynchronize(e1);
+    float ms = 0.0f;
+    if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if (err != hipSuccess) return fail_a(-2, std::string("ismpc_a_plan_table_kernel: ") + hipGetErrorString(err));
+    h->build_ms = ms;
+    h->table = true; h->tab_feet = static_cast<double*>(feet); h->tab_rules = static_cast<FeetParams*>(rules);
+    h->c.tab_x = tx; h->c.tab_y = ty; h->c.nplans = n_plans;
+    HIP_TRY_A(hipMemcpy(h->c_dev, &h->c, sizeof(DevA), hipMemcpyHostToDevice));
+    return 0;
+}
+}  // namespace
+
+int ismpc_a_create_plans(const ismpc_a_params* p, const ismpc_a_gait* gaits, int n_plans, int device, ismpc_a_handle** out)
+{
+    if (!p) return fail_a(-1, "ismpc_a_create_plans: null params");
+    if (!gaits) return fail_a(-1, "ismpc_a_create_plans: null gaits");
+    if (!out) return fail_a(-1, "ismpc_a_create_plans: null out");
+    *out = nullptr;
+    if (n_plans < 1) return fail_a(-1, "ismpc_a_create_plans: n_plans must be at least 1");
+    if (n_plans > ISMPC_A_MAX_PLANS) return fail_a(-1, "ismpc_a_create_plans: n_plans beyond ISMPC_A_MAX_PLANS");
+    if (p->n_gait < 16) return fail_a(-1, "ismpc_a_create_plans: n_gait must be at least 16");
+    for (int k = 0; k < n_plans; ++k) {
+        if (gaits[k].n_gait != p->n_gait) return fail_a(-1, "ismpc_a_create_plans: n_gait of gaits[" + std::to_string(k) + "] differs from the parameters'");
+        if (gaits[k].gait != 0 && gaits[k].gait != 1) return fail_a(-1, "ismpc_a_create_plans: gait of gaits[" + std::to_string(k) + "] is neither 0 (trot) nor 1 (walk)");
+    }
+    try {
+        // plan 0 on the host: what the plain launches, the centreline tables and the tails are built from, as ismpc_a_create does
+        std::vector<double> fp0((size_t)(p->n_gait + 1) * 8), ce0((size_t)p->n_gait * 2);
+        if (ismpc_a_plan(&gaits[0], fp0.data(), ce0.data()) < 0) return -1;
+        ismpc_a_handle* h = nullptr;
+        if (int rc = ismpc_a_create(p, ce0.data(), device, &h)) return rc;
+        int rc;
+        {
+            DeviceGuardA guard_(device);
+            rc = guard_.err != hipSuccess ? fail_a(-2, "hipSetDevice failed") : build_plan_table(h, gaits, n_plans);
+        }
+        if (rc) { ismpc_a_destroy(h); return rc; }
+        *out = h;
+    } catch (const std::bad_alloc&) {
+        return fail_a(-3, "ismpc_a_create_plans: out of host memory");
+    }
+    return 0;
+}
+
+int ismpc_a_plans_info(const ismpc_a_handle* h, int* n_plans)
+{
+    if (!h || !n_plans) return fail_a(-1, "ismpc_a_plans_info: null argument");
+    *n_plans = h->c.nplans;
+    return 0;
+}
+
+double ismpc_a_plans_build_ms(const ismpc_a_handle* h) { return (h && h->table) ? (double)h->build_ms : -1.0; }
+
+int ismpc_a_get_plan(ismpc_a_handle* h, int plan, double* foot_plan, double* center)
+{
+    if (!h) return fail_a(-1, "ismpc_a_get_plan: null handle");
+    if (!h->table) return fail_a(-1, "ismpc_a_get_plan: needs a handle of ismpc_a_create_plans");
+    if (plan < 0 || plan >= h->c.nplans) return fail_a(-1, "ismpc_a_get_plan: plan index out of range");
+    ON_DEVICE_A(h);
+    const int NG = h->p.n_gait, used = plan_used_rows(h->gaits[plan].gait, NG);
+    if (foot_plan) HIP_TRY_A(hipMemcpy(foot_plan, h->tab_feet + (size_t)plan * plan_table_rows(NG) * 8, sizeof(double) * 8 * (size_t)used, hipMemcpyDeviceToHost));
+    if (center) {
+        std::vector<double> x(NG), y(NG);
+        HIP_TRY_A(hipMemcpy(x.data(), h->c.tab_x + (size_t)plan * NG, sizeof(double) * NG, hipMemcpyDeviceToHost));
+        HIP_TRY_A(hipMemcpy(y.data(), h->c.tab_y + (size_t)plan * NG, sizeof(double) * NG, hipMemcpyDeviceToHost));
+        for (int i = 0; i < NG; ++i) { center[i * 2] = x[i]; center[i * 2 + 1] = y[i]; }
+    }
+    return used;
+}
+
+int ismpc_a_initial_state_plan(const ismpc_a_handle* h, int plan, ismpc_a_state* st)
+{
+    if (!h || !st) return fail_a(-1, "ismpc_a_initial_state_plan: null argument");
+    if (!h->table) return fail_a(-1, "ismpc_a_initial_state_plan: needs a handle of ismpc_a_create_plans");
+    if (plan < 0 || plan >= h->c.nplans) return fail_a(-1, "ismpc_a_initial_state_plan: plan index out of range");
+    ON_DEVICE_A(h);
+    double f0[2];
+    HIP_TRY_A(hipMemcpy(&f0[0], h->c.tab_x + (size_t)plan * h->p.n_gait, sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY_A(hipMemcpy(&f0[1], h->c.tab_y + (size_t)plan * h->p.n_gait, sizeof(double), hipMemcpyDeviceToHost));
+    std::memset(st, 0, sizeof(*st));
+    const double disp_C = h->gaits[plan].disp_C;
+    st->x = disp_C / 2; st->xz = disp_C / 2;                  // :52-57
+    st->cur_x = f0[0]; st->cur_y = f0[1];                     // :58-59
+    st->fc = 1; st->j = 1;
+    return 0;
 }
 
 int ismpc_a_reserve(ismpc_a_handle* h, int max_batch)
@@ -722,6 +880,14 @@ static int feet_upload(ismpc_a_handle* h, const ismpc_a_gait* gaits, const doubl
     }
     return 0;
 }
+// ... and the rules where the feet kernels read them (ismpc_a_handle::feet_rules), after feet_upload's caller has settled h->feet
+static int feet_rules_upload(ismpc_a_handle* h)
+{
+    if (!h->feet_rules) { HIP_TRY_A(hipMalloc((void**)&h->feet_rules, 5 * sizeof(FeetParams))); h->allocs.push_back(h->feet_rules); }
+    FeetParams r[5] = {h->feet_set.p[0], h->feet_set.p[1], h->feet_set.p[2], h->feet_set.p[3], h->feet};
+    HIP_TRY_A(hipMemcpy(h->feet_rules, r, sizeof(r), hipMemcpyHostToDevice));
+    return 0;
+}
 
 int ismpc_a_feet_init_device(ismpc_a_handle* h, const ismpc_a_gait* g, const double* foot_plan_host, int rows, int batch,
                              double* feet_dev, void* stream)
@@ -729,6 +895,8 @@ int ismpc_a_feet_init_device(ismpc_a_handle* h, const ismpc_a_gait* g, const dou
     if (!h || !g || !foot_plan_host || rows < 2 || batch < 0 || (batch > 0 && !feet_dev)) return fail_a(-1, "bad argument");
     ON_DEVICE_A(h);
     if (int rc = feet_upload(h, g, foot_plan_host, rows, 1, &h->feet)) return rc;
+    if (int rc = feet_rules_upload(h)) return rc;
+    h->feet_from_table = false;
     const int rp = h->feet.rows;
     if (batch > 0) {
         hipLaunchKernelGGL(ismpc_a_feet_fill, dim3(std::min(1024, (int)(((size_t)batch * rp * 8 + 255) / 256))), dim3(256), 0, static_cast<hipStream_t>(stream),
@@ -744,14 +912,36 @@ int ismpc_a_feet_init_inst_device(ismpc_a_handle* h, const ismpc_a_gait* gaits, 
 {
     if (!h || !gaits || !foot_plans_host || rows < 2 || nplans < 1 || nplans > 4 || batch < 0 || (batch > 0 && (!feet_dev || !inst_dev)))
         return fail_a(-1, "bad argument");
+    if (h->table) return fail_a(-1, "ismpc_a_feet_init_inst_device: a plan-table handle starts its feet with ismpc_a_feet_init_plans_device (the table is the source)");
     if (nplans != h->c.nplans) return fail_a(-1, "feet: one gait record and one foot plan per base plan of the handle (ismpc_a_create + ismpc_a_add_plan)");
     ON_DEVICE_A(h);
     if (int rc = feet_upload(h, gaits, foot_plans_host, rows, nplans, h->feet_set.p)) return rc;
     h->feet_plans = nplans; h->feet = h->feet_set.p[0];
+    if (int rc = feet_rules_upload(h)) return rc;
     const int rp = h->feet.rows;
     if (batch > 0) {
         hipLaunchKernelGGL(ismpc_a_feet_fill_inst, dim3(std::min(1024, (int)(((size_t)batch * rp * 8 + 255) / 256))), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           (const double*)h->feet_base, inst_dev, nplans, feet_dev, rp, batch);
+                           h->feet_tab(true), inst_dev, feet_dev, rp, batch);
+        HIP_TRY_A(hipGetLastError());
+    }
+    return 0;
+}
+
+// Plan-table handles: the blocks come from the table's foot plans, the rules are the table's (nothing is uploaded).
+int ismpc_a_feet_init_plans_device(ismpc_a_handle* h, int rows, int batch, const ismpc_a_inst* inst_dev, double* feet_dev, void* stream)
+{
+    if (!h) return fail_a(-1, "ismpc_a_feet_init_plans_device: null handle");
+    if (!h->table) return fail_a(-1, "ismpc_a_feet_init_plans_device: needs a handle of ismpc_a_create_plans");
+    if (rows < 2 || rows > h->p.n_gait + 1) return fail_a(-1, "ismpc_a_feet_init_plans_device: rows must be in [2, n_gait + 1]");
+    if (batch < 0 || (batch > 0 && !feet_dev)) return fail_a(-1, "ismpc_a_feet_init_plans_device: negative batch, or batch > 0 with a null feet_dev");
+    ON_DEVICE_A(h);
+    const int rp = rows + ISMPC_A_FEET_PAD;
+    const ismpc_a_gait& g = h->gaits[0];
+    h->feet.gait = g.gait; h->feet.rows = rp; h->feet.phi = g.phi; h->feet.disp_i = g.disp_i; h->feet.disp_o = g.disp_o; h->feet.disp_forw = g.disp_forw;
+    h->feet_plans = h->c.nplans; h->feet_from_table = true;
+    if (batch > 0) {
+        hipLaunchKernelGGL(ismpc_a_feet_fill_inst, dim3(std::min(1024, (int)(((size_t)batch * rp * 8 + 255) / 256))), dim3(256), 0, static_cast<hipStream_t>(stream),
+                           h->feet_tab(true), inst_dev, feet_dev, rp, batch);
         HIP_TRY_A(hipGetLastError());
     }
     return 0;
@@ -765,10 +955,8 @@ static int tick_feet(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, con
     ON_DEVICE_A(h);                                                 // the feet launch below runs on the handle's device too
     int rc = tick_launch(h, batch, state_dev, inst_dev, push_dev, out_dev, stream, history, mc);
     if (rc || batch == 0) return rc;
-    FeetParamsSet fs = h->feet_set;
-    if (!inst_dev) fs.p[0] = h->feet;
     hipLaunchKernelGGL(ismpc_a_feet_kernel, dim3((batch + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       fs, inst_dev, inst_dev ? h->feet_plans : 1, (const ismpc_a_state*)h->prev, (const ismpc_a_out*)out_dev, feet_dev, batch);
+                       h->feet_tab(inst_dev != nullptr), inst_dev, (const ismpc_a_state*)h->prev, (const ismpc_a_out*)out_dev, feet_dev, h->feet.rows, batch);
     HIP_TRY_A(hipGetLastError());
     return 0;
 }
@@ -889,9 +1077,10 @@ int ismpc_a_rollout_mc_feet_device(ismpc_a_handle* h, int batch, ismpc_a_state* 
         HIP_TRY_A(hipGetLastError());
     }
     if (feet_summary_dev) {
+        FeetTab ft = h->feet_tab(inst_dev != nullptr);
+        if (ft.base == h->feet_base) ft.nplans = std::min(ft.nplans, h->feet_base_plans);     // the base plans the last ismpc_a_feet_init*_device left on the device
         hipLaunchKernelGGL(ismpc_a_feet_summary_kernel, dim3((batch + FEET_SUMMARY_WAVES - 1) / FEET_SUMMARY_WAVES), dim3(64 * FEET_SUMMARY_WAVES), 0, s,
-                           (const double*)feet_dev, (const double*)h->feet_base, inst_dev, inst_dev ? std::min(h->feet_plans, h->feet_base_plans) : 1, h->feet.rows, batch,
-                           feet_summary_dev);
+                           (const double*)feet_dev, ft, inst_dev, h->feet.rows, batch, feet_summary_dev);
         HIP_TRY_A(hipGetLastError());
     }
     return 0;
@@ -966,12 +1155,9 @@ int ismpc_a_foot_trajectories_device(ismpc_a_handle* h, int batch, const ismpc_a
     if (batch == 0) return 0;
     const int chunks = (sim_duration + FOOT_CHUNK_ROWS - 1) / FOOT_CHUNK_ROWS;
     if ((long long)batch * chunks > 0x7fffffffLL) return fail_a(-1, "ismpc_a_foot_trajectories_device: batch x sim_duration beyond one launch");
-    const int nplans = inst_dev ? h->feet_plans : 1;
-    FootGaits gaits{};
-    for (int k = 0; k < nplans; ++k) gaits.gait[k] = inst_dev ? h->feet_set.p[k].gait : h->feet.gait;
     const size_t lds = sizeof(double) * 8 * (size_t)std::min(h->feet.rows, FOOT_PLAN_ROWS);
     hipLaunchKernelGGL(ismpc_a_foot_trajectories_kernel, dim3(batch * chunks), dim3(FOOT_THREADS), lds, static_cast<hipStream_t>(stream),
-                       gaits, nplans, inst_dev, h->p.step, feet_dev, h->feet.rows, sim_duration, chunks, batch, dst_dev, nrows_dev);
+                       h->feet_tab(inst_dev != nullptr), inst_dev, h->p.step, feet_dev, h->feet.rows, sim_duration, chunks, batch, dst_dev, nrows_dev);
     HIP_TRY_A(hipGetLastError());
     return 0;
 }

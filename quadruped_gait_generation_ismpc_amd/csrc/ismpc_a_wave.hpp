@@ -456,7 +456,7 @@ void ismpc_a_tick_wave(const DevA* __restrict__ cp, const ismpc_a_state* __restr
         const float rstep = dummy_ip ? 0.5f : (PI ? pre[inst].rstep : c.rstep);
         const double inv_dsm1 = PI ? (dummy_ip ? 1.0 : pre[inst].inv_dsm1) : 0.0, inv_ds = dummy_ip ? 1.0 : (PI ? pre[inst].inv_ds : c.inv_ds);
         const double ieta = dummy_ip ? 1.0 : (PI ? pre[inst].ieta : c.ieta);
-        const double* fs = PI ? (axis == 0 ? c.plan_x[plan] : c.plan_y[plan]) : (axis == 0 ? c.fsx : c.fsy);
+        const double* fs = PI ? (axis == 0 ? c.tab_x : c.tab_y) + (size_t)plan * c.n_gait : (axis == 0 ? c.fsx : c.fsy);
         const double* cl = st.rebuilt ? (axis == 0 ? c.clx1 : c.cly1) : (axis == 0 ? c.clx0 : c.cly0);
         const double cloff = st.rebuilt ? off : 0.0;
         const int ncl = PI ? (c.n_gait - 1) * step_ : c.ncl;

@@ -51,7 +51,9 @@ EXPORTS_A = ["ismpc_a_params_default", "ismpc_a_gait_default", "ismpc_a_plan", "
              "ismpc_a_add_plan", "ismpc_a_tick_batch_inst_device", "ismpc_a_rollout_inst_device", "ismpc_a_set_warm_history", "ismpc_a_reserve", "ismpc_a_set_precision",
              "ismpc_a_last_deferred", "ismpc_a_feet_init_inst_device", "ismpc_a_tick_feet_batch_inst_device",
              "ismpc_a_rollout_feet_inst_device", "ismpc_a_rollout_mc_device", "ismpc_a_rollout_mc_feet_device",
-             "ismpc_a_foot_trajectories_device"]
+             "ismpc_a_foot_trajectories_device", "ismpc_a_create_plans", "ismpc_a_plans_info", "ismpc_a_plans_build_ms", "ismpc_a_get_plan",
+             "ismpc_a_initial_state_plan", "ismpc_a_plan_steps", "ismpc_a_feet_init_plans_device"]
+MAX_PLANS = 0x0fffffff  # ISMPC_A_MAX_PLANS
 HAVE_F32 = True        # the QP solve also exists in fp32 (GaitGenerator(..., precision="f32"))
 FEET_PAD = 8
 
@@ -91,6 +93,13 @@ def _l():
         lib.ismpc_a_rollout_mc_device.argtypes = [vp, ci, vp, vp, ci, vp, ci, ci, vp, vp, vp]; lib.ismpc_a_rollout_mc_device.restype = ci
         lib.ismpc_a_rollout_mc_feet_device.argtypes = [vp, ci, vp, vp, ci, vp, ci, ci, vp, vp, vp, vp, vp]; lib.ismpc_a_rollout_mc_feet_device.restype = ci
         lib.ismpc_a_foot_trajectories_device.argtypes = [vp, ci, vp, vp, ci, vp, vp, vp]; lib.ismpc_a_foot_trajectories_device.restype = ci
+        lib.ismpc_a_create_plans.argtypes = [C.POINTER(ParamsA), vp, ci, ci, C.POINTER(vp)]; lib.ismpc_a_create_plans.restype = ci
+        lib.ismpc_a_plans_info.argtypes = [vp, C.POINTER(ci)]; lib.ismpc_a_plans_info.restype = ci
+        lib.ismpc_a_plans_build_ms.argtypes = [vp]; lib.ismpc_a_plans_build_ms.restype = cd
+        lib.ismpc_a_get_plan.argtypes = [vp, ci, vp, vp]; lib.ismpc_a_get_plan.restype = ci
+        lib.ismpc_a_initial_state_plan.argtypes = [vp, ci, vp]; lib.ismpc_a_initial_state_plan.restype = ci
+        lib.ismpc_a_plan_steps.argtypes = [C.POINTER(GaitA), vp]; lib.ismpc_a_plan_steps.restype = ci
+        lib.ismpc_a_feet_init_plans_device.argtypes = [vp, ci, ci, vp, vp, vp]; lib.ismpc_a_feet_init_plans_device.restype = ci
         _bound = True
     return lib
 
@@ -122,6 +131,18 @@ def plan(g):
     if used < 0:
         raise IsmpcAError(_l().ismpc_a_last_error().decode())
     return fp[:used].copy(), ce
+
+
+CLIP_HALF_LATERAL, CLIP_HALF_FORWARD, CLIP_STEP_LATERAL, CLIP_STEP_FORWARD = 1, 2, 4, 8
+
+
+def plan_steps(g):
+    """The clipped step and first half step of a plan (ismpc_a_plan_steps): (array [xs, ys, xsd, ysd], the CLIP_* branches that ran)."""
+    s = np.zeros(4)
+    rc = _l().ismpc_a_plan_steps(C.byref(g), s.ctypes.data_as(C.c_void_p))
+    if rc < 0:
+        raise IsmpcAError(_l().ismpc_a_last_error().decode())
+    return s, rc
 
 
 def foot_trajectories(g, step, foot_plan, sim_duration=2000):
@@ -164,6 +185,75 @@ class GaitGenerator:
         if _l().ismpc_a_set_precision(self._h, 1 if precision == "f32" else 0) != 0:
             msg = _l().ismpc_a_last_error().decode(); self.close()
             raise IsmpcAError(msg)
+
+    @classmethod
+    def from_gaits(cls, params, gaits, device=0, precision="f64"):
+        """A plan-table handle (ismpc_a_create_plans): one base plan per GaitA record of `gaits`, all of them built on the device; an
+        instance names its plan in INST_A["plan"].  Plan 0 is gaits[0]: without INST_A records the generator is GaitGenerator(params,
+        plan(gaits[0])[1]).  add_plan and feet_init_inst_torch are refused; feet start with feet_init_plans_torch."""
+        if precision not in ("f64", "f32"):
+            raise ValueError("precision must be 'f64' or 'f32'")
+        gaits = list(gaits)
+        self = cls.__new__(cls)
+        self.precision, self.params, self._h = precision, params, None
+        self.gaits = gaits
+        ga = (GaitA * max(len(gaits), 1))(*gaits)
+        h = C.c_void_p()
+        rc = _l().ismpc_a_create_plans(C.byref(params), C.cast(ga, C.c_void_p), len(gaits), int(device), C.byref(h))
+        if rc != 0:
+            raise IsmpcAError(f"ismpc_a_create_plans: {rc}: {_l().ismpc_a_last_error().decode()}")
+        self._h = h
+        self.center = plan(gaits[0])[1]
+        if _l().ismpc_a_set_precision(self._h, 1 if precision == "f32" else 0) != 0:
+            msg = _l().ismpc_a_last_error().decode(); self.close()
+            raise IsmpcAError(msg)
+        return self
+
+    @property
+    def n_plans(self):
+        """Base plans of the handle: the table's count, or 1 + the add_plan calls."""
+        n = C.c_int(0)
+        if _l().ismpc_a_plans_info(self._h, C.byref(n)) != 0:
+            raise IsmpcAError(_l().ismpc_a_last_error().decode())
+        return n.value
+
+    @property
+    def plans_build_ms(self):
+        """Milliseconds the generator launch of from_gaits took on the device."""
+        return _l().ismpc_a_plans_build_ms(self._h)
+
+    def get_plan(self, k):
+        """Plan k of a plan-table generator, read back from the device: (foot_plan [rows, 8], center [n_gait, 2]) as plan() returns them."""
+        ng = self.params.n_gait
+        fp = np.zeros((ng + 1, 8)); ce = np.zeros((ng, 2))
+        used = _l().ismpc_a_get_plan(self._h, int(k), fp.ctypes.data_as(C.c_void_p), ce.ctypes.data_as(C.c_void_p))
+        if used < 0:
+            raise IsmpcAError(_l().ismpc_a_last_error().decode())
+        return fp[:used].copy(), ce
+
+    def initial_state_plan(self, k, batch=1):
+        """The state the scripts start from for plan k's gait record (ismpc_a_initial_state_plan)."""
+        st = np.zeros(1, dtype=STATE_A)
+        if _l().ismpc_a_initial_state_plan(self._h, int(k), st.ctypes.data_as(C.c_void_p)) != 0:
+            raise IsmpcAError(_l().ismpc_a_last_error().decode())
+        return np.repeat(st, batch)
+
+    def feet_init_plans_torch(self, inst_u8, rows=None):
+        """Plan-table generators: every instance's foot plan block from the table's foot plan of its plan (ismpc_a_feet_init_plans_device;
+        inst_u8: CUDA uint8 [batch, 32] INST_A records).  rows: plan rows per instance, default what feet_init_inst_torch takes for the
+        same gaits (n_gait + 1 when a walk plan is among them, else n_gait).  Returns float64 tensor [batch, rows + FEET_PAD, 8]."""
+        import torch
+        assert inst_u8.is_cuda and inst_u8.dtype == torch.uint8 and inst_u8.dim() == 2 and inst_u8.shape[1] == 32 and inst_u8.is_contiguous()
+        if rows is None:
+            rows = self.params.n_gait + (1 if any(g.gait == WALK for g in getattr(self, "gaits", [])) else 0)
+        b = inst_u8.shape[0]
+        feet = torch.empty((b, int(rows) + FEET_PAD, 8), dtype=torch.float64, device=inst_u8.device)
+        stream = torch.cuda.current_stream(inst_u8.device).cuda_stream
+        rc = _l().ismpc_a_feet_init_plans_device(self._h, int(rows), b, C.c_void_p(inst_u8.data_ptr()), C.c_void_p(feet.data_ptr()),
+                                                 C.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise IsmpcAError(_l().ismpc_a_last_error().decode())
+        return feet
 
     def close(self):
         if getattr(self, "_h", None) and _l is not None:
