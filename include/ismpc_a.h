@@ -151,6 +151,43 @@ int ismpc_a_tick_batch_inst_device(ismpc_a_handle* h, int batch, ismpc_a_state* 
 int ismpc_a_rollout_inst_device(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, const ismpc_a_inst* inst_dev,
                                 int ticks, ismpc_a_out* out_traj_dev, void* stream);
 
+/* ---- THE WHOLE DECISION and the PREDICTED HORIZON of a tick.
+ * ismpc_a_tick_batch_horizon_device is ismpc_a_tick_batch_device (inst_dev NULL) or ismpc_a_tick_batch_inst_device (batch records) with two
+ * more outputs.  It serves plain, ismpc_a_add_plan and plan-table handles in either precision and runs whichever kernel the handle
+ * dispatches (the wave kernel at every rows-per-lane value, the per-footstep-count launches, the fp32 launch and its fp64 re-solve, the
+ * workgroup kernel), in an instantiation that also stores the decision; state, out_dev, the working-set history and the deferred counter
+ * are exactly what the plain call produces.
+ *
+ * dec_dev: [batch][2 axes][C + F] doubles, C and F those of ismpc_a_horizon_shape (F = the handle's maximum).  Per instance and axis
+ * u[0 .. C-1] = predicted_xzd(1 .. C), then f[0 .. F-1] = predicted_xfs(1 .. F) as ABSOLUTE footsteps: the scripts' decisionVariables order.
+ *   dec[.., 0] is out.u0 and dec[.., C] is out.f0, bit for bit (f[k] = cur + (double)f_rel[k], formed in fp64 as f0 is).
+ *   With the fp32 solve the values are the fp32 iterate widened, as u0 / f0 are.
+ *   A per-instance record with inst.F < F gets f[inst.F .. F-1] = 0.0 (written, not left as found).
+ *   An instance the tick leaves alone (ISMPC_A_ST_BAD_INDEX, ISMPC_A_ST_OVERFLOW): u all 0.0, every f[k] = out.f0 (the current footstep).
+ *   An infeasible QP or one that hit the iteration limit returns its last iterate, as u0 does.
+ *
+ * pred_dev: NULL (no prediction, no further launch) or [batch][2 axes][4][C] doubles: x, xd, xz, zc at samples i = 1 .. C, written by
+ * ismpc_a_predict_kernel behind the solver launch(es).
+ *   Sample 1 of x, xd, xz is the state the tick just wrote, byte for byte; samples 2 .. C continue the scripts' loop `compute prediction`
+ *   (quad_walk_no_plots.m:297-314 with up_to = C) from it: s = A_upd s + B_upd u[i-1] with this instance's A_upd, B_upd, in the expression
+ *   order of the tick's own state update.
+ *   zc_i is the centre of sample i's ZMP band, w_i g[pf_i] + (1 - w_i) g[pf_i + 1] with g = [cur, f_1 .. f_F] (cur: the PRE-tick current
+ *   footstep, f from dec), pf_i and rem_i by the integer rule of the scripts' mapping (pf grows by one when j + i >= step (fc + pf);
+ *   rem_i = step (fc + pf_i) - (j + i)) and w_i = 1 when rem_i > ds, else rem_i / ds.  |xz_i - zc_i| <= w / 2 is the ZMP constraint of row i.
+ *   Every sample of an instance the tick left alone is a quiet NaN.
+ *
+ * Returns -1 before the device is touched, ismpc_a_last_error naming the function and the argument: null handle, negative batch, null
+ * out_dev, null dec_dev, batch > 0 with a null state_dev.  batch = 0 returns 0.  A closed loop with horizons is the caller-driven loop of
+ * this call with ismpc_a_set_warm_history(h, 1). */
+int ismpc_a_horizon_shape(const ismpc_a_handle* h, int* C, int* F);
+int ismpc_a_tick_batch_horizon_device(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev,
+                                      const ismpc_a_inst* inst_dev,            /* NULL: the handle's parameters; else batch records */
+                                      const double* push_dev,                  /* NULL, or batch x 2 */
+                                      ismpc_a_out* out_dev,                    /* required */
+                                      double* dec_dev,                         /* required: batch x 2 x (C + F) */
+                                      double* pred_dev,                        /* NULL, or batch x 2 x 4 x C */
+                                      void* stream);
+
 /* ---- PLAN-TABLE handles: any number of base plans, built on the device.
  * ismpc_a_create_plans takes n_plans gait records (host) instead of one centre.  Plan 0 is gaits[0]: everything ismpc_a_create builds
  * from `center` (centreline tables, tails, the plan of the plain launches) is built from the host's ismpc_a_plan(&gaits[0]), so every

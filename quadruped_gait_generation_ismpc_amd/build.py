@@ -36,8 +36,9 @@ def _stale(target, sources, flags):
         return True
 
 
-UNITS = ["ismpc_hip.hip", "ismpc_sweep.hip", "ismpc_a_hip.hip", "ismpc_a_wave_rl2.hip", "ismpc_a_wave_rl3.hip", "ismpc_a_wave_rl4.hip", "ismpc_group.hip", "ismpc_tables.cpp"]
-HEADERS = ["ismpc_tables.hpp", "ismpc_sweep.hpp", "ismpc_a_dev.hpp", "ismpc_a_wave.hpp", "ismpc_a_block.hpp", "ismpc_a_feet.hpp", "ismpc_a_feet_files.hpp", "ismpc_a_plans.hpp", "ismpc_wave_prims.hpp", "ismpc_host.hpp",
+UNITS = ["ismpc_hip.hip", "ismpc_sweep.hip", "ismpc_a_hip.hip", "ismpc_a_wave_rl2.hip", "ismpc_a_wave_rl3.hip", "ismpc_a_wave_rl4.hip", "ismpc_a_wave_rl2_hz.hip", "ismpc_a_wave_rl3_hz.hip", "ismpc_a_wave_rl4_hz.hip",
+         "ismpc_group.hip", "ismpc_tables.cpp"]
+HEADERS = ["ismpc_tables.hpp", "ismpc_sweep.hpp", "ismpc_a_dev.hpp", "ismpc_a_wave.hpp", "ismpc_a_block.hpp", "ismpc_a_feet.hpp", "ismpc_a_feet_files.hpp", "ismpc_a_plans.hpp", "ismpc_a_horizon.hpp", "ismpc_wave_prims.hpp", "ismpc_host.hpp",
            "ismpc_b_common.hpp", "ismpc_b_dense.hpp", "ismpc_b_affine.hpp", "ismpc_b_group.hpp", "ismpc_rccl_load.hpp"]
 PUBLIC = ["ismpc.h", "ismpc_a.h", "ismpc_group.h"]
 BASE_FLAGS = ["-O3", "-fno-slp-vectorize", "-std=c++17", "-fPIC"]

@@ -194,9 +194,12 @@ __device__ __forceinline__ double row_value(Shared& s, const DevA& c, int tid)
     return 0.0;
 }
 
+// HZ: the tick also stores the whole decision of every QP into `dec` (ismpc_a_tick_batch_horizon_device; the layout is stated in
+// include/ismpc_a.h).  <false> is the tick as it always was: `dec` is never read and no store exists.
+template <bool HZ>
 __global__ __launch_bounds__(T)
 void ismpc_a_tick_kernel(const DevA c, const ismpc_a_state* __restrict__ state_in, ismpc_a_state* __restrict__ state,
-                         const double* __restrict__ push, ismpc_a_out* __restrict__ out, int batch)
+                         const double* __restrict__ push, ismpc_a_out* __restrict__ out, int batch, double* __restrict__ dec)
 {
     __shared__ Shared s;
     extern __shared__ double sinv_lds[];            // ldq x ldq when the launch asked for it (c.sinv_in_lds)
@@ -449,6 +452,14 @@ void ismpc_a_tick_kernel(const DevA c, const ismpc_a_state* __restrict__ state_i
 
         // ---- LIP update (:297-322), footstep bookkeeping (:522-556), outputs
         __syncthreads();
+        if constexpr (HZ) {
+            // u[0 .. C-1] and the absolute footsteps f[1 .. F] as they stand in LDS: slot 0 is u0 and slot C is f0 below, to the bit; an
+            // instance the tick leaves alone has u = 0 and every footstep = f0 = cur
+            const bool left = (status & (ISMPC_A_ST_BAD_INDEX | ISMPC_A_ST_OVERFLOW)) != 0;
+            double* dq = dec + (size_t)work * (size_t)(C + F);
+            if (tid < C) dq[tid] = left ? 0.0 : s.u[tid];
+            if (tid < F) dq[C + tid] = left ? cur : s.f[tid + 1];
+        }
         if (tid == 0) {
             const double u0 = (status & (ISMPC_A_ST_BAD_INDEX | ISMPC_A_ST_OVERFLOW)) ? 0.0 : s.u[0];
             const double f0 = (status & (ISMPC_A_ST_BAD_INDEX | ISMPC_A_ST_OVERFLOW)) ? cur : s.f[1];

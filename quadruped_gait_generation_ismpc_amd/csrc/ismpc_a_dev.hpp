@@ -52,7 +52,7 @@ struct WaveLaunch {
     const DevA* c_dev; int F;                      // the handle's constants in device memory; footsteps in the horizon (kernel shape)
     const ismpc_a_state* prev; ismpc_a_state* state; const ismpc_a_inst* inst; const double* push; ismpc_a_out* out;
     int batch; int* work_counter; unsigned long long* hist; int hist_load;
-    int precision; int cus; int* occ_cache;       // occ_cache: per handle, [F - 3][precision x per-instance], 0 = not queried yet
+    int precision; int cus; int* occ_cache;       // occ_cache: per handle, [decision stored][F - 3][precision x per-instance], 0 = not queried yet
     const int* order; const int* count_ptr;       // NULL, or the instances of this launch (device list + device count): see tick_launch
     int claim_chunk;                              // QPs a wavefront takes from the work counter per atomic
     int static_q;                                 // sixteenths of the launch's QPs that are dealt out statically (no atomics) first
@@ -61,11 +61,16 @@ struct WaveLaunch {
     int grid_cap;                                 // > 0: at most this many workgroups (the re-solve launch)
     hipStream_t stream;
     const PiPre* pre = nullptr;                   // per-instance launches (inst != NULL): the prologue's record of every instance
+    double* dec = nullptr;                        // launch_wave_rl*_hz only: the whole decision, batch x 2 x (C + DevA::F) doubles (ismpc_a.h)
 };
 
 // Implemented in ismpc_a_wave_rl{2,3,4}.hip.  Return 0, -1 (no instantiation for this F) or -2 (HIP error, *err set).
 int launch_wave_rl2(const WaveLaunch& L, hipError_t* err);
 int launch_wave_rl3(const WaveLaunch& L, hipError_t* err);
 int launch_wave_rl4(const WaveLaunch& L, hipError_t* err);
+// The same kernels with the decision stores (L.dec required), in ismpc_a_wave_rl{2,3,4}_hz.hip.
+int launch_wave_rl2_hz(const WaveLaunch& L, hipError_t* err);
+int launch_wave_rl3_hz(const WaveLaunch& L, hipError_t* err);
+int launch_wave_rl4_hz(const WaveLaunch& L, hipError_t* err);
 
 }  // namespace ismpc_a

@@ -11,6 +11,8 @@
 //                           four foot files of every instance, the host writer's bits)
 //   ismpc_a_plans.hpp       ismpc_a_plan_table_kernel (the plan generators on the device: every plan of a plan-table handle in one launch,
 //                           the host's ismpc_a_plan to the bit)
+//   ismpc_a_horizon.hpp     ismpc_a_predict_kernel (the predicted CoM / ZMP horizon of a tick from its whole decision; the decision itself is
+//                           stored by the Horizon<> instantiations of the wave kernel, ismpc_a_wave_rl*_hz.hip, and ismpc_a_tick_kernel<true>)
 //   ismpc_wave_prims.hpp    wavefront prefix sum (shared with Formulation B)
 //   ismpc_host.hpp          device guard, early return on a HIP error, growth of scratch (shared by the three ABIs)
 //   this file               the error string; host geometry (linspace_m, centreline, ismpc_a_plan, ismpc_a_foot_trajectories, the text
@@ -39,6 +41,7 @@
 #include "ismpc_a_feet.hpp"
 #include "ismpc_a_feet_files.hpp"
 #include "ismpc_a_plans.hpp"
+#include "ismpc_a_horizon.hpp"
 
 namespace {
 
@@ -99,7 +102,7 @@ struct ismpc_a_handle {
         return per_inst ? FeetTab{feet_rules, feet_base, feet_plans, feet.rows} : FeetTab{feet_rules + 4, feet_base, 1, feet.rows};
     }
     bool use_wave = true; int wave_blocks = 0;           // structured wavefront-per-QP kernel (default) vs workgroup-per-QP
-    int cus = 0, wave_occ[16] = {0};                     // resident workgroups per CU of the wave kernels ([F - 3][precision x per-instance])
+    int cus = 0, wave_occ[32] = {0};                     // resident workgroups per CU of the wave kernels ([decision stored][F - 3][precision x per-instance])
     ismpc_a::PiPre* pre = nullptr; int pre_cap = 0;       // per-instance launches: the prologue's record per instance
     int* order = nullptr; int order_cap = 0;             // per-instance launches: instance lists by footstep count (4 x cap) + 4 counters
     bool bucket_by_F = false;                            // ISMPC_A_BUCKET=1: one launch per footstep count instead of one launch of the widest kernel
@@ -533,7 +536,9 @@ int ismpc_a_create(const ismpc_a_params* p, const double* center, int device, is
         }
     }
     if (!rc && c.sinv_in_lds) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(ismpc_a_tick_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(ismpc_a_tick_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)((size_t)c.ldq * c.ldq * sizeof(double))) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void*>(ismpc_a_tick_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)((size_t)c.ldq * c.ldq * sizeof(double))) != hipSuccess) c.sinv_in_lds = 0, h->slots *= 4;
     }
     if (!rc && hipMemcpy(h->c_dev, &h->c, sizeof(DevA), hipMemcpyHostToDevice) != hipSuccess) rc = fail_a(-2, "constants upload failed");
@@ -717,9 +722,10 @@ int ismpc_a_reserve(ismpc_a_handle* h, int max_batch)
 // The handle's scratch (prev, pre, hist, order, defer_list) outlives the call that allocated it and is used by later calls on
 // whatever stream those pass: it grows through ISMPC_GROW_ASYNC (ismpc_host.hpp), which drains the previous launch's stream first.
 static int tick_launch(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, const ismpc_a_inst* inst_dev, const double* push_dev,
-                       ismpc_a_out* out_dev, void* stream, int history = -1, const McTick* mc = nullptr)
+                       ismpc_a_out* out_dev, void* stream, int history = -1, const McTick* mc = nullptr, double* dec_dev = nullptr)
 {
     // mc: a tick of the disturbed closed loop (rollout_mc_a): its prologue in place of the plain one, everything else as always
+    // dec_dev: the solver launch(es) run in the form that also stores every QP's whole decision there (ismpc_a_tick_batch_horizon_device)
     if (!h || batch < 0 || (batch > 0 && !state_dev)) return fail_a(-1, "bad argument");
     if (batch == 0) return 0;
     ON_DEVICE_A(h);
@@ -762,15 +768,15 @@ static int tick_launch(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, c
                                h->precision, h->cus, h->wave_occ, nullptr, nullptr, 1, 0, 0, nullptr, nullptr, 0, s};
         // QPs per work-counter atomic (scripts/claim_sweep.sh): one device-wide atomic per QP costs 10-50 % when QPs are short (two rows
         // per lane, the fp32 solve at three, closed-loop ticks); pairs coarsen the balance too much when they are long
-        WL.static_q = h->static_q; WL.pre = inst_dev ? h->pre : nullptr;
+        WL.static_q = h->static_q; WL.pre = inst_dev ? h->pre : nullptr; WL.dec = dec_dev;
         WL.claim_chunk = h->claim_chunk > 0 ? h->claim_chunk : ((rl <= 2 || (h->precision == 1 && rl == 3) || hist_load) ? 2 : 1);
         hipError_t werr = hipSuccess;
         int wrc = -1;
         auto go = [&](const ismpc_a::WaveLaunch& W) {
             switch (rl) {
-                case 1: case 2: return ismpc_a::launch_wave_rl2(W, &werr);
-                case 3: return ismpc_a::launch_wave_rl3(W, &werr);
-                case 4: return ismpc_a::launch_wave_rl4(W, &werr);
+                case 1: case 2: return W.dec ? ismpc_a::launch_wave_rl2_hz(W, &werr) : ismpc_a::launch_wave_rl2(W, &werr);
+                case 3: return W.dec ? ismpc_a::launch_wave_rl3_hz(W, &werr) : ismpc_a::launch_wave_rl3(W, &werr);
+                case 4: return W.dec ? ismpc_a::launch_wave_rl4_hz(W, &werr) : ismpc_a::launch_wave_rl4(W, &werr);
                 default: return -1;
             }
         };
@@ -815,7 +821,9 @@ static int tick_launch(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, c
         if (h->precision != 0) return fail_a(-1, "the fp32 solve needs the structured kernel: 3 <= F <= 6 and C <= 256");
     }
     const int grid = std::min(2 * batch, h->slots);
-    hipLaunchKernelGGL(ismpc_a_tick_kernel, dim3(grid), dim3(T), h->c.sinv_in_lds ? (size_t)h->c.ldq * h->c.ldq * sizeof(double) : 0, s, h->c, (const ismpc_a_state*)h->prev, state_dev, push_dev, out_dev, batch);
+    const size_t sinv_bytes = h->c.sinv_in_lds ? (size_t)h->c.ldq * h->c.ldq * sizeof(double) : 0;
+    if (dec_dev) hipLaunchKernelGGL(ismpc_a_tick_kernel<true>, dim3(grid), dim3(T), sinv_bytes, s, h->c, (const ismpc_a_state*)h->prev, state_dev, push_dev, out_dev, batch, dec_dev);
+    else hipLaunchKernelGGL(ismpc_a_tick_kernel<false>, dim3(grid), dim3(T), sinv_bytes, s, h->c, (const ismpc_a_state*)h->prev, state_dev, push_dev, out_dev, batch, (double*)nullptr);
     HIP_TRY_A(hipGetLastError());
     return 0;
 }
@@ -857,6 +865,35 @@ int ismpc_a_tick_batch_inst_device(ismpc_a_handle* h, int batch, ismpc_a_state* 
 {
     if (batch > 0 && !inst_dev) return fail_a(-1, "null per-instance parameter array");
     return tick_launch(h, batch, state_dev, inst_dev, push_dev, out_dev, stream);
+}
+
+// ---- the tick's whole decision and predicted horizon
+int ismpc_a_horizon_shape(const ismpc_a_handle* h, int* C, int* F)
+{
+    if (!h) return fail_a(-1, "ismpc_a_horizon_shape: null handle");
+    if (!C || !F) return fail_a(-1, "ismpc_a_horizon_shape: null C or F");
+    *C = h->c.C; *F = h->c.F;
+    return 0;
+}
+
+int ismpc_a_tick_batch_horizon_device(ismpc_a_handle* h, int batch, ismpc_a_state* state_dev, const ismpc_a_inst* inst_dev, const double* push_dev,
+                                      ismpc_a_out* out_dev, double* dec_dev, double* pred_dev, void* stream)
+{
+    // every argument error before the handle is looked at, let alone the device (as ismpc_a_rollout_mc_device)
+    if (batch < 0) return fail_a(-1, "ismpc_a_tick_batch_horizon_device: negative batch");
+    if (!out_dev) return fail_a(-1, "ismpc_a_tick_batch_horizon_device: null out_dev (the prediction reads the tick's status from it)");
+    if (!dec_dev) return fail_a(-1, "ismpc_a_tick_batch_horizon_device: null dec_dev");
+    if (batch > 0 && !state_dev) return fail_a(-1, "ismpc_a_tick_batch_horizon_device: batch > 0 with a null state_dev");
+    if (!h) return fail_a(-1, "ismpc_a_tick_batch_horizon_device: null handle");
+    if (int rc = tick_launch(h, batch, state_dev, inst_dev, push_dev, out_dev, stream, -1, nullptr, dec_dev)) return rc;
+    if (batch == 0 || !pred_dev) return 0;
+    ON_DEVICE_A(h);
+    const unsigned grid = (unsigned)((2ll * batch + HZ_PAIRS - 1) / HZ_PAIRS);
+    hipLaunchKernelGGL(ismpc_a_predict_kernel, dim3(grid), dim3(HZ_PAIRS), 0, static_cast<hipStream_t>(stream), h->c, (const ismpc_a_state*)h->prev,
+                       (const ismpc_a_state*)state_dev, inst_dev, (const ismpc_a::PiPre*)(inst_dev ? h->pre : nullptr), (const ismpc_a_out*)out_dev,
+                       (const double*)dec_dev, pred_dev, batch);
+    HIP_TRY_A(hipGetLastError());
+    return 0;
 }
 
 int ismpc_a_feet_rows(const ismpc_a_handle* h) { return h ? h->feet.rows : -1; }

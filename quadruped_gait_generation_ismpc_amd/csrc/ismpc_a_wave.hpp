@@ -1,5 +1,6 @@
 // Wavefront-per-QP kernel of Formulation A: the STRUCTURED dual active-set solver (docs/models/proto_structured.py is its numpy
-// model).  Included by one translation unit per rows-per-lane value (ismpc_a_wave_rl{2,3,4}.hip).
+// model).  Included by one translation unit per rows-per-lane value (ismpc_a_wave_rl{2,3,4}.hip)
+// and, for the instantiations that also store the whole decision, by ismpc_a_wave_rl{2,3,4}_hz.hip.
 //
 // The per-axis QP of one instance (walking/quad_walk_no_plots.m:153-293):
 //     min 1/2 |u|^2 + Qf/2 |f - p|^2      u = ZMP velocities (C), f = footsteps (F)
@@ -311,18 +312,29 @@ template <typename R, int RL, int F, bool PI> constexpr int wave_min_blocks()
                           : (RL <= 2 ? ISMPC_A_OCC_F64_RL2 : ((RL == 3 && !PI) ? ISMPC_A_OCC_F64_RL3 : ISMPC_A_OCC_F64_RL4));
 }
 
+// The arithmetic type of an instantiation, and whether it stores the whole decision (ismpc_a_tick_batch_horizon_device):
+// ismpc_a_tick_wave<double | float, ...> is the tick as it always was -- `dec` is never read, no store exists -- and
+// ismpc_a_tick_wave<Horizon<double | float>, ...> the same solve with the decision stores at its output.  A type, not a fifth template
+// argument, so that the plain instantiations keep their symbol names (profiles and bench.py name them).
+template <typename Real> struct Horizon { using type = Real; };
+template <typename RT> struct RealOf { using type = RT; static constexpr bool horizon = false; };
+template <typename Real> struct RealOf<Horizon<Real>> { using type = Real; static constexpr bool horizon = true; };
+
 // RL = ZMP rows per lane (C <= 64 RL), F = footsteps in the horizon (m = 2F+1 border columns).
 // PI: per-instance gait parameters (ismpc_a_inst): height, Qf, step, ds, F <= the template F, base plan.
-template <typename R, int RL, int F, bool PI>
-__global__ __launch_bounds__(WG, (wave_min_blocks<R, RL, F, PI>()))
+template <typename RT, int RL, int F, bool PI>
+__global__ __launch_bounds__(WG, (wave_min_blocks<typename RealOf<RT>::type, RL, F, PI>()))
 void ismpc_a_tick_wave(const DevA* __restrict__ cp, const ismpc_a_state* __restrict__ state_in, ismpc_a_state* __restrict__ state,
                        const ismpc_a_inst* __restrict__ ipar, const double* __restrict__ push, ismpc_a_out* __restrict__ out, int batch,
                        int* __restrict__ work_counter, unsigned long long* __restrict__ hist, int hist_load,
                        const int* __restrict__ order, const int* __restrict__ count_ptr, const int claim_chunk_, const int static_q,
-                       const int order_is_qp, int* __restrict__ defer_list, int* __restrict__ defer_count, const PiPre* __restrict__ pre)
+                       const int order_is_qp, int* __restrict__ defer_list, int* __restrict__ defer_count, const PiPre* __restrict__ pre,
+                       double* __restrict__ dec)
 {
     // the re-solve launch behind an fp32 launch that handed nothing over (the usual case) leaves before it builds its tables
     if (order_is_qp && *count_ptr == 0) return;
+    using R = typename RealOf<RT>::type;
+    constexpr bool HZ = RealOf<RT>::horizon;
     using NM = Num<R>;
     const DevA& c = *cp;                                   // handle constants, read from memory where they are used (by value they would
     constexpr int m = 2 * F + 1;                           // sit in 70 scalar registers for the whole persistent loop)
@@ -1585,6 +1597,26 @@ void ismpc_a_tick_wave(const DevA* __restrict__ cp, const ismpc_a_state* __restr
         const bool ok = (status & (ISMPC_A_ST_BAD_INDEX | ISMPC_A_ST_OVERFLOW)) == 0;
         const double u0 = ok ? (double)rl(u[0], 0) : 0.0;
         const double df0 = ok ? (double)rl(fr, 1) : 0.0;                          // first footstep, relative to the current one
+        if constexpr (HZ) {
+            // The whole decision of this QP, [C + c.F] doubles (c.F: the handle's footstep count, the stride whatever this launch's shape):
+            // every lane its RL consecutive rows -- a contiguous run per wavefront, padding rows >= C never stored -- and lanes 1 .. c.F
+            // the footsteps as ABSOLUTE positions, by the expression f0 is formed with below (slot 0 is u0 and slot C is f0 to the bit).
+            // A footstep beyond this instance's count is 0.0; an instance the tick leaves alone has u = 0 and every footstep = f0 = cur.
+            double* dq = dec + ((size_t)inst * 2 + axis) * (size_t)(C + c.F);
+#pragma unroll
+            for (int k = 0; k < RL; ++k) {
+                const int row = lane * RL + k;
+                if (row < C) dq[row] = ok ? (double)u[k] : 0.0;
+            }
+            if (lane >= 1 && lane <= c.F) {
+                const ismpc_a_state* sp = state_in + inst;
+                asm volatile("" : "+v"(sp));                                     // read again, per lane: as the record below
+                const double curl = axis == 0 ? sp->cur_x : sp->cur_y;
+                int Fl = F;
+                if (PI) { const ismpc_a_inst* ipp = ipar + inst; asm volatile("" : "+v"(ipp)); Fl = ipp->F; }
+                dq[C + lane - 1] = !ok ? curl : (lane <= Fl ? curl + (double)fr : 0.0);
+            }
+        }
         if (lane == 0) {
             // The instance's record is READ AGAIN here, by this one lane, instead of staying live -- in scalar registers, it is wave-uniform --
             // across the whole solve: position, velocity, ZMP, current footstep, counters and (per-instance) the gait parameters were a
@@ -1650,11 +1682,12 @@ void ismpc_a_tick_wave(const DevA* __restrict__ cp, const ismpc_a_state* __restr
 }
 
 // ---- launch: persistent grid = exactly the workgroups that are resident at once (registers / LDS decide how many per CU)
-template <typename R, int RL, int F, bool PI>
+template <typename RT, int RL, int F, bool PI>
 inline int launch_one(const WaveLaunch& L, hipError_t* err)
 {
-    auto kern = ismpc_a_tick_wave<R, RL, F, PI>;
-    int& occ = L.occ_cache[(F - 3) * 4 + (sizeof(R) == 4 ? 2 : 0) + (PI ? 1 : 0)];
+    using R = typename RealOf<RT>::type;
+    auto kern = ismpc_a_tick_wave<RT, RL, F, PI>;
+    int& occ = L.occ_cache[(RealOf<RT>::horizon ? 16 : 0) + (F - 3) * 4 + (sizeof(R) == 4 ? 2 : 0) + (PI ? 1 : 0)];
     if (occ == 0) {
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, WG, 0) != hipSuccess || nb < 1) nb = 1;
@@ -1663,11 +1696,12 @@ inline int launch_one(const WaveLaunch& L, hipError_t* err)
     int grid = std::min((2 * L.batch + 3) / 4, L.cus * occ);
     if (L.grid_cap > 0) grid = std::min(grid, L.grid_cap);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WG), 0, L.stream, L.c_dev, L.prev, L.state, L.inst, L.push, L.out, L.batch, L.work_counter, L.hist, L.hist_load,
-                       L.order, L.count_ptr, L.claim_chunk, L.static_q, L.order_is_qp, L.defer_list, L.defer_count, L.pre);
+                       L.order, L.count_ptr, L.claim_chunk, L.static_q, L.order_is_qp, L.defer_list, L.defer_count, L.pre, L.dec);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { if (err) *err = e; return -2; }
     return 0;
 }
+// (R below: double, float, or Horizon<double>, Horizon<float>)
 template <typename R, int RL, int F>
 inline int launch_pi(const WaveLaunch& L, hipError_t* err) { return L.inst ? launch_one<R, RL, F, true>(L, err) : launch_one<R, RL, F, false>(L, err); }
 template <typename R, int RL>
@@ -1683,5 +1717,11 @@ inline int launch_f(const WaveLaunch& L, hipError_t* err)
 }
 template <int RL>
 inline int launch_wave(const WaveLaunch& L, hipError_t* err) { return L.precision == 1 ? launch_f<float, RL>(L, err) : launch_f<double, RL>(L, err); }
+// ... and the instantiations that store the decision (L.dec), in translation units of their own (ismpc_a_wave_rl{2,3,4}_hz.hip)
+template <int RL>
+inline int launch_wave_horizon(const WaveLaunch& L, hipError_t* err)
+{
+    return L.precision == 1 ? launch_f<Horizon<float>, RL>(L, err) : launch_f<Horizon<double>, RL>(L, err);
+}
 
 }  // namespace ismpc_a

@@ -52,7 +52,8 @@ EXPORTS_A = ["ismpc_a_params_default", "ismpc_a_gait_default", "ismpc_a_plan", "
              "ismpc_a_last_deferred", "ismpc_a_feet_init_inst_device", "ismpc_a_tick_feet_batch_inst_device",
              "ismpc_a_rollout_feet_inst_device", "ismpc_a_rollout_mc_device", "ismpc_a_rollout_mc_feet_device",
              "ismpc_a_foot_trajectories_device", "ismpc_a_create_plans", "ismpc_a_plans_info", "ismpc_a_plans_build_ms", "ismpc_a_get_plan",
-             "ismpc_a_initial_state_plan", "ismpc_a_plan_steps", "ismpc_a_feet_init_plans_device"]
+             "ismpc_a_initial_state_plan", "ismpc_a_plan_steps", "ismpc_a_feet_init_plans_device",
+             "ismpc_a_horizon_shape", "ismpc_a_tick_batch_horizon_device"]
 MAX_PLANS = 0x0fffffff  # ISMPC_A_MAX_PLANS
 HAVE_F32 = True        # the QP solve also exists in fp32 (GaitGenerator(..., precision="f32"))
 FEET_PAD = 8
@@ -100,6 +101,8 @@ def _l():
         lib.ismpc_a_initial_state_plan.argtypes = [vp, ci, vp]; lib.ismpc_a_initial_state_plan.restype = ci
         lib.ismpc_a_plan_steps.argtypes = [C.POINTER(GaitA), vp]; lib.ismpc_a_plan_steps.restype = ci
         lib.ismpc_a_feet_init_plans_device.argtypes = [vp, ci, ci, vp, vp, vp]; lib.ismpc_a_feet_init_plans_device.restype = ci
+        lib.ismpc_a_horizon_shape.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]; lib.ismpc_a_horizon_shape.restype = ci
+        lib.ismpc_a_tick_batch_horizon_device.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]; lib.ismpc_a_tick_batch_horizon_device.restype = ci
         _bound = True
     return lib
 
@@ -279,6 +282,44 @@ class GaitGenerator:
                                             C.c_void_p(stream) if stream else None)
         if rc != 0:
             raise IsmpcAError(_l().ismpc_a_last_error().decode())
+
+    def horizon_shape(self):
+        """(C, F) of the handle (ismpc_a_horizon_shape): a tick's decision is 2 x (C + F) doubles per instance, its prediction 2 x 4 x C."""
+        c, f = C.c_int(0), C.c_int(0)
+        if _l().ismpc_a_horizon_shape(self._h, C.byref(c), C.byref(f)) != 0:
+            raise IsmpcAError(_l().ismpc_a_last_error().decode())
+        return c.value, f.value
+
+    def tick_horizon_device(self, batch, state_ptr, out_ptr, dec_ptr, pred_ptr=None, push_ptr=None, inst_ptr=None, stream=None):
+        """ismpc_a_tick_batch_horizon_device on raw device pointers: the tick with its whole decision (dec_ptr: batch x 2 x (C + F) doubles)
+        and, with pred_ptr, the predicted horizon (batch x 2 x 4 x C doubles: x, xd, xz, zc at samples 1 .. C)."""
+        opt = lambda p: C.c_void_p(p) if p else None
+        rc = _l().ismpc_a_tick_batch_horizon_device(self._h, int(batch), opt(state_ptr), opt(inst_ptr), opt(push_ptr), opt(out_ptr), opt(dec_ptr),
+                                                    opt(pred_ptr), opt(stream))
+        if rc != 0:
+            raise IsmpcAError(_l().ismpc_a_last_error().decode())
+
+    def tick_horizon_torch(self, state_u8, push=None, inst_u8=None, want_pred=True):
+        """One tick (tick_torch, or tick_inst_torch with inst_u8) that also returns every QP's whole decision and the predicted horizon.
+        state_u8: CUDA uint8 [batch, 96], updated in place; push: None or CUDA float64 [batch, 2]; inst_u8: None or CUDA uint8 [batch, 32].
+        Returns (out_u8 [batch, 80], dec float64 [batch, 2, C + F], pred float64 [batch, 2, 4, C] or None) on the state's device.  dec: the
+        ZMP velocities u[0 .. C-1] then the absolute footsteps f[0 .. F-1] per axis; pred: x, xd, xz and the band centre zc at samples
+        1 .. C (NaN for an instance the tick left alone)."""
+        import torch
+        b = state_u8.shape[0]
+        assert state_u8.is_cuda and state_u8.dtype == torch.uint8 and state_u8.shape[1] == 96 and state_u8.is_contiguous()
+        if inst_u8 is not None:
+            assert inst_u8.is_cuda and inst_u8.dtype == torch.uint8 and inst_u8.shape == (b, 32) and inst_u8.is_contiguous() and inst_u8.device == state_u8.device
+        if push is not None:
+            assert push.is_cuda and push.dtype == torch.float64 and tuple(push.shape) == (b, 2) and push.is_contiguous() and push.device == state_u8.device
+        c, f = self.horizon_shape()
+        out = torch.empty((b, 80), dtype=torch.uint8, device=state_u8.device)
+        dec = torch.empty((b, 2, c + f), dtype=torch.float64, device=state_u8.device)
+        pred = torch.empty((b, 2, 4, c), dtype=torch.float64, device=state_u8.device) if want_pred else None
+        stream = torch.cuda.current_stream(state_u8.device).cuda_stream
+        self.tick_horizon_device(b, state_u8.data_ptr(), out.data_ptr(), dec.data_ptr(), pred.data_ptr() if want_pred else None,
+                                 push.data_ptr() if push is not None else None, inst_u8.data_ptr() if inst_u8 is not None else None, stream)
+        return out, dec, pred
 
     def rollout_device(self, batch, state_ptr, ticks, traj_ptr=None, stream=None):
         rc = _l().ismpc_a_rollout_device(self._h, int(batch), C.c_void_p(state_ptr), int(ticks),

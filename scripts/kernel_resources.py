@@ -11,7 +11,8 @@ md = None
 if "--md" in args:
     md = args[args.index("--md") + 1]; del args[args.index("--md"):args.index("--md") + 2]
 rows = []
-for src in ("ismpc_hip.hip", "ismpc_a_hip.hip", "ismpc_a_wave_rl2.hip", "ismpc_a_wave_rl3.hip", "ismpc_a_wave_rl4.hip"):
+for src in ("ismpc_hip.hip", "ismpc_a_hip.hip", "ismpc_a_wave_rl2.hip", "ismpc_a_wave_rl3.hip", "ismpc_a_wave_rl4.hip",
+            "ismpc_a_wave_rl2_hz.hip", "ismpc_a_wave_rl3_hz.hip", "ismpc_a_wave_rl4_hz.hip"):
     with tempfile.TemporaryDirectory() as td:
         r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17", "-fPIC", "-I", os.path.join(ROOT, "include"),
                             "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, src), "-o", os.path.join(td, "x.o")]
