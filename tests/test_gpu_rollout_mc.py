@@ -101,11 +101,11 @@ def push_tensor(q, pushes):
     return q.to_device(pushes.reshape(-1)).view(pushes.shape[0], pushes.shape[1], 32)
 
 
-def run_mc(q, s, recs, ticks, pushes=None, stride=1, want_traj=True, want_summary=True, expect_kernel=True):
+def run_mc(q, s, recs, ticks, pushes=None, stride=1, want_traj=True, want_summary=True, expect_kernel=True, first_frame=0):
     """One call of the entry point under test.  Returns (trajectory records or None, summary records or None, final state records)."""
     import torch
     st = q.to_device(recs)
-    traj, summ = s.rollout_mc_torch(st, 0, ticks, pushes=None if pushes is None else push_tensor(q, pushes), stride=stride,
+    traj, summ = s.rollout_mc_torch(st, first_frame, ticks, pushes=None if pushes is None else push_tensor(q, pushes), stride=stride,
                                     want_traj=want_traj, want_summary=want_summary)
     torch.cuda.synchronize()
     info = s.launch_info()
@@ -117,19 +117,20 @@ def run_mc(q, s, recs, ticks, pushes=None, stride=1, want_traj=True, want_summar
             q.from_device(st, q.TICK_IN))
 
 
-def run_plain(q, s, recs, ticks):
+def run_plain(q, s, recs, ticks, expect_kernel=True, first_frame=0):
     import torch
     st = q.to_device(recs)
-    traj = s.rollout_torch(st, 0, ticks)
+    traj = s.rollout_torch(st, first_frame, ticks)
     torch.cuda.synchronize()
     info = s.launch_info()
-    assert info["family"] == "rollout_quad" and "mc" not in info, info
+    assert (info["family"] == "rollout_quad") == expect_kernel and "mc" not in info, info
     return q.from_device(traj, q.TICK_OUT), q.from_device(st, q.TICK_IN)
 
 
-def segmented(q, s, recs, pushes, ticks):
+def segmented(q, s, recs, pushes, ticks, first_frame=0):
     """The reference computation: plain rollouts (ismpc_rollout_device) between the push ticks, torch adding dv to the com_vel bytes of
-    the state tensor in between -- one fp64 add per component and entry, in the order the cursor rule applies them."""
+    the state tensor in between -- one fp64 add per component and entry, in the order the cursor rule applies them.  (Push ticks count
+    from the call's tick 0, frames from first_frame.)"""
     import torch
     st = q.to_device(recs)
     v = st.view(torch.float64)                                   # [B, 9]: com_pos, com_vel, simulation_time, counters
@@ -142,13 +143,13 @@ def segmented(q, s, recs, pushes, ticks):
     parts, a = [], 0
     for b in sorted(events):
         if b > a:
-            parts.append(s.rollout_torch(st, a, b - a))
+            parts.append(s.rollout_torch(st, first_frame + a, b - a))
         for k in sorted(events[b]):
             idx = torch.tensor([i for i, _ in events[b][k]], device=st.device)
             dv = torch.tensor(np.stack([pushes["dv"][i, j] for i, j in events[b][k]]), device=st.device)
             v[idx, 3:6] = v[idx, 3:6] + dv
         a = b
-    parts.append(s.rollout_torch(st, a, ticks - a))
+    parts.append(s.rollout_torch(st, first_frame + a, ticks - a))
     torch.cuda.synchronize()
     return q.from_device(torch.cat(parts), q.TICK_OUT), q.from_device(st, q.TICK_IN)
 
